@@ -5,6 +5,9 @@ launched by the driver via torch.distributed.run, one rank per GPU over RCCL).
 Measures the BASELINE.json metric — images/sec, whole node, synthetic
 3x224x224 data, random-init weights, bf16 compute, per-rank batch 256,
 SyncBN on RCCL when world_size > 1 — and prints ONE JSON line from rank 0.
+The steps run at ``--lr`` (default 0: same kernels, weights stay put, so
+outputs repeat run to run). ``--dump-outputs DIR`` also writes what the last
+timed step handed back; ``--full`` is where secondary measurements belong (none today).
 """
 
 import argparse
@@ -29,7 +32,66 @@ def parse_args():
     p.add_argument("--graph", type=int, default=-1,
                    help="capture the step in a hipGraph: -1 auto "
                         "(on for 1 GPU), 0/1 force")
+    p.add_argument("--lr", type=float, default=0.0,
+                   help="SGD learning rate, reported as config.lr. 0 "
+                        "(default) runs the whole step but leaves the weights "
+                        "at their seeded values, so outputs repeat from run "
+                        "to run; 0.2 is the project's base rate")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write what the last step "
+                        "handed back (logits, loss, BN/classifier gradients "
+                        "and momentum) to DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements; bench.py has "
+                        "none beyond the headline figure, so this is "
+                        "currently the same as a plain run")
     return p.parse_args()
+
+
+def _dump_outputs(out_dir, arrays, max_bytes=60 << 20):
+    """Write ``arrays`` (name -> tensor) as float32 ``out_dir/<name>.npy``.
+    The arrays share ``max_bytes``; one over its share is cut to a fixed,
+    seeded sample of its rows (dim 0), kept in order; an array whose single
+    row is over the share is flattened and sampled by element."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = max_bytes // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach().float().cpu()
+        if t.dim() == 0 or 4 * t.shape[1:].numel() > share:
+            t = t.reshape(-1)
+        max_rows = share // (4 * max(t.shape[1:].numel(), 1))
+        if t.shape[0] > max_rows:
+            g = torch.Generator(device="cpu").manual_seed(1234)
+            rows = torch.randperm(t.shape[0], generator=g)[:max_rows]
+            t = t[rows.sort().values]
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+
+
+def _step_results(net, optimizer, last):
+    """What the last step handed back: its return values, and the gradients
+    and momentum it left on the parameters that no atomic-add kernel feeds
+    (1-D BN/bias parameters and the 2-D classifier weight). Those depend on
+    the loss backward, every dgrad and BN-backward kernel and the SGD
+    kernel, and are the same from run to run; the conv weight gradients come
+    out of fp32 atomics and differ by a bf16 ulp between runs, so they stay
+    out of the dump."""
+    logits, loss = last
+    grads, moms = [], []
+    for p in net.parameters():
+        if p.dim() > 2 or p.grad is None:
+            continue
+        grads.append(p.grad.detach().float().reshape(-1))
+        buf = optimizer.state.get(p, {}).get("momentum_buffer")
+        if buf is not None:
+            moms.append(buf.detach().float().reshape(-1))
+    arrays = {"logits": logits, "loss": loss}
+    if grads:
+        arrays["grads_bn_fc"] = torch.cat(grads)
+    if moms:
+        arrays["momentum_bn_fc"] = torch.cat(moms)
+    return arrays
 
 
 def _self_launch(args):
@@ -91,11 +153,16 @@ def main():
     cfg.freeze()
 
     dtype = torch.bfloat16 if use_bf16 else torch.float32
+    # fixed seed: same arguments -> same initial weights (the synthetic batch
+    # is seeded by the loader), so two builds can be compared output for output
+    torch.manual_seed(1234)
     net = T.build_network(device)
     if world_size > 1:
         net = DistributedDataParallel(net, bucket_cap_mb=cfg.TRAIN.BUCKET_CAP_MB)
     optimizer = utils.construct_optimizer(net)
-    utils.set_lr(optimizer, 0.2)
+    # default rate 0: the same kernels run, the weights stay put, and the
+    # outputs repeat from run to run (why: docs/BENCHMARKING.md)
+    utils.set_lr(optimizer, args.lr)
     net.train()
 
     loader = DeviceSyntheticLoader(batch, im_size=224, num_classes=1000,
@@ -114,10 +181,22 @@ def main():
         optimizer.zero_grad(set_to_none=zero_none)
         loss.backward()
         optimizer.step()
-        return loss
+        return outputs.detach(), loss.detach()
+
+    def untimed_step():
+        # With set_to_none the grad pointers move every step, so HIPSGD
+        # rewrites its pinned chunk table on the host and copies it to the
+        # device asynchronously; a host that runs a step ahead overwrites the
+        # table before the previous copy has executed and the update reads
+        # wrong pointers (NaN weights from the third step on). Draining the
+        # device after each untimed eager step keeps the state that the timed
+        # steps start from, and the dumped outputs, well defined.
+        step()
+        if has_gpu:
+            torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        step()
+        untimed_step()
 
     # hipGraph capture of the whole train step: the inner loop replays one
     # graph instead of ~900 eager launches. Multi-rank too — RCCL collectives
@@ -126,17 +205,18 @@ def main():
     # to eager below.
     use_graph = bool(has_gpu) if args.graph == -1 else bool(args.graph)
     graph = None
+    last = None  # (logits, loss) of the most recent timed step
     if use_graph:
         try:
             torch.cuda.synchronize()
             side = torch.cuda.Stream()
             with torch.cuda.stream(side):
                 for _ in range(2):
-                    step()
+                    untimed_step()
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                step()
+                last = step()  # static tensors, refilled by every replay
             graph.replay()
             torch.cuda.synchronize()
         except Exception as exc:  # pragma: no cover - fall back to eager
@@ -161,7 +241,7 @@ def main():
         if graph is not None:
             graph.replay()
         else:
-            step()
+            last = step()
     if has_gpu:
         torch.cuda.synchronize()
     if world_size > 1:
@@ -178,6 +258,9 @@ def main():
     global_batch = batch * world_size
     images_per_sec = args.steps * global_batch / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
+
+    if args.dump_outputs and rank == 0 and last is not None:
+        _dump_outputs(args.dump_outputs, _step_results(net, optimizer, last))
 
     if rank == 0:
         print(json.dumps({
@@ -201,6 +284,7 @@ def main():
                 "parallelism": f"dp{world_size}",
                 "syncbn": use_syncbn,
                 "hipgraph": graph is not None,
+                "lr": args.lr,
             },
         }))
 
