@@ -552,7 +552,8 @@ __global__ __launch_bounds__(256) void mhsa_bwd_kv_kernel(MhsaBwdKVParams p) {
 struct MhsaRelGradParams {
   const float* dr;          // [rows, M] (dRW or dRH)
   const __hip_bfloat16* q;  // strided rows
-  float* out;               // [M, D]
+  float* out;               // [M, D] zeroed, or part[row blocks][M*D]
+  int64_t pstride;          // 0: atomics into out; else workspace slot stride
   int64_t rows;
   int M, D, rows_per_block;
   int heads, L;
@@ -614,8 +615,17 @@ __global__ __launch_bounds__(256) void mhsa_rel_grad_kernel(
       ++bb;
     }
   }
-  for (int m = 0; m < mn; ++m)
-    atomicAdd(&p.out[(int64_t)(m0 + m) * p.D + d], acc[m] * p.scale);
+  // deterministic mode (pstride != 0): row block blockIdx.x stores into its
+  // own slot; the two halves cover [0, M) and d < D, one writer per element
+  float* dst = p.out + (int64_t)blockIdx.x * p.pstride;
+  if (p.pstride != 0) {
+    for (int m = 0; m < mn; ++m)
+      emit_partial<true>(&dst[(int64_t)(m0 + m) * p.D + d], acc[m] * p.scale);
+  } else {
+    for (int m = 0; m < mn; ++m)
+      emit_partial<false>(&dst[(int64_t)(m0 + m) * p.D + d],
+                          acc[m] * p.scale);
+  }
 }
 
 // ---- per-row rel-logit tables: out[row, m] = sum_d q[row, d] rel[m, d] ----
@@ -767,15 +777,27 @@ std::vector<at::Tensor> mhsa_bwd(at::Tensor dO, at::Tensor P, at::Tensor q,
 
   auto grw = at::empty({MW, D}, fopts);
   auto grh = at::empty({MH, D}, fopts);
-  hipMemsetAsync(grw.data_ptr(), 0, grw.numel() * 4, cur_stream());
-  hipMemsetAsync(grh.data_ptr(), 0, grh.numel() * 4, cur_stream());
   const int64_t rows = (int64_t)B * L;
   const int rpb = 128;
+  const int rblocks = (int)ceil_div(rows, rpb);
+  const bool det = is_deterministic();  // sampled per launch
+  at::Tensor part;  // deterministic mode: [rblocks][M*D] per table, no memset
+  if (det) {
+    part = at::empty({(int64_t)rblocks, (int64_t)std::max(MW, MH) * D}, fopts);
+  } else {
+    hipMemsetAsync(grw.data_ptr(), 0, grw.numel() * 4, cur_stream());
+    hipMemsetAsync(grh.data_ptr(), 0, grh.numel() * 4, cur_stream());
+  }
   for (int which = 0; which < 2; ++which) {
     MhsaRelGradParams rp;
     rp.dr = which == 0 ? drw.data_ptr<float>() : drh.data_ptr<float>();
     rp.q = (const __hip_bfloat16*)q.data_ptr();
     rp.out = which == 0 ? grw.data_ptr<float>() : grh.data_ptr<float>();
+    rp.pstride = 0;
+    if (det) {
+      rp.out = part.data_ptr<float>();
+      rp.pstride = (int64_t)(which == 0 ? MW : MH) * D;
+    }
     rp.rows = rows;
     rp.M = which == 0 ? MW : MH;
     rp.D = D;
@@ -784,9 +806,13 @@ std::vector<at::Tensor> mhsa_bwd(at::Tensor dO, at::Tensor P, at::Tensor q,
     rp.L = L;
     rp.qpix = qpix;
     rp.scale = (float)scale;
-    hipLaunchKernelGGL(mhsa_rel_grad_kernel,
-                       dim3((int)ceil_div(rows, rpb)), dim3(256), 0,
+    hipLaunchKernelGGL(mhsa_rel_grad_kernel, dim3(rblocks), dim3(256), 0,
                        cur_stream(), rp);
+    if (det)  // stream-ordered, so the two tables can share one workspace
+      ordered_reduce<float>(
+          part.data_ptr<float>(),
+          which == 0 ? grw.data_ptr<float>() : grh.data_ptr<float>(), rblocks,
+          rp.pstride, 1.f);
   }
   return {dqk_out, dv_out, grw, grh};
 }

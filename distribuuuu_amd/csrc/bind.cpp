@@ -134,6 +134,9 @@ at::Tensor mhsa_rel_tables(at::Tensor q, at::Tensor rel, int64_t rows,
 at::Tensor aug_crop_flip_norm(at::Tensor raw, at::Tensor meta, int64_t S,
                               std::vector<double> mean,
                               std::vector<double> std, at::ScalarType dtype);
+// det_reduce.hip
+void set_deterministic(bool on);
+bool is_deterministic();
 // sgd.hip
 void sgd_step(at::Tensor table, double lr, double momentum,
               double dampening, double weight_decay, bool nesterov);
@@ -200,4 +203,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mhsa_bwd", &mhsa_bwd);
   m.def("mhsa_rel_tables", &mhsa_rel_tables);
   m.def("aug_crop_flip_norm", &aug_crop_flip_norm);
+  m.def("set_deterministic", &set_deterministic);
+  m.def("is_deterministic", &is_deterministic);
 }

@@ -145,6 +145,32 @@ inline hipStream_t cur_stream() {
   return at::cuda::getCurrentCUDAStream().stream();
 }
 
+// ---------------------------------------------------------------------------
+// deterministic mode (det_reduce.hip, docs/DETERMINISM.md)
+// ---------------------------------------------------------------------------
+// Process-global switch; initial value from DISTRIBUUUU_DETERMINISTIC=1.
+// Host launchers sample it per call, so a captured graph keeps the mode it
+// was captured in.
+void set_deterministic(bool on);
+bool is_deterministic();
+
+// out[i] = cast(scale * sum_{p=0..P-1, ascending} part[p*n + i]) on the
+// current stream; Tout = float or __hip_bfloat16. part is a fully written
+// [P][n] fp32 workspace (no memset needed).
+template <typename Tout>
+void ordered_reduce(const float* part, Tout* out, int P, int64_t n,
+                    float scale);
+
+// Cross-block fp32 partial: one atomic into the shared accumulator (default)
+// or a plain store into this block's own workspace slot (deterministic).
+template <bool DET>
+DEV_INLINE void emit_partial(float* dst, float v) {
+  if constexpr (DET)
+    *dst = v;
+  else
+    atomicAdd(dst, v);
+}
+
 // NHWC (channels_last) accessor checks
 inline void check_nhwc(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.dim() == 4, name, " must be 4-D");

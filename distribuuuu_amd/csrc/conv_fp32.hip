@@ -211,7 +211,9 @@ __global__ __launch_bounds__(256) void conv_igemm_fp32_kernel(
 // 64x64 (k x rsc) tile per block, m-steps of 16 staged m-major in LDS
 // ([16][64+pad] per operand) and read column-wise for the
 // mfma_f32_16x16x4f32 operand maps; split-m chunks accumulate with fp32
-// atomics directly into gw (no cast pass — gw IS fp32).
+// atomics directly into gw (no cast pass — gw IS fp32). Deterministic mode
+// (docs/DETERMINISM.md): each chunk stores into its own slot of a
+// [chunks][Kt*RSC] workspace and ordered_reduce sums the slots in order.
 // ---------------------------------------------------------------------------
 constexpr int WF_BM = 64, WF_BN = 64, WF_BK = 16;
 constexpr int WF_LD = WF_BN + 4;        // column-read pad
@@ -220,7 +222,7 @@ constexpr int WF_CHUNK = 64;            // m-steps per block chunk (1024 px)
 struct WgradF32Params {
   const float* x;   // [N,H,W,Ct]
   const float* gy;  // [N,Ho,Wo,Kt]
-  float* gw;        // [Kt, R*S*Cg] zeroed fp32
+  float* gw;        // [Kt, R*S*Cg] zeroed fp32, or part[chunks][pstride]
   int N, H, W, Ct, Kt;
   int R, S, Cg, Kg;
   int sh, sw, ph, pw, dh, dw;
@@ -228,12 +230,16 @@ struct WgradF32Params {
   int M, RSC;
   int ktiles, ntiles, chunks;
   unsigned long long magicHoWo, magicWo;
+  // deterministic mode: workspace slot stride (0 otherwise); last, so every
+  // other kernarg keeps its offset
+  int64_t pstride;
 };
 
 DEV_INLINE int magic_div_f(int m, unsigned long long magic) {
   return (int)(((unsigned long long)(unsigned)m * magic) >> 47);
 }
 
+template <bool DET>
 __global__ __launch_bounds__(256) void conv_wgrad_fp32_kernel(
     WgradF32Params p) {
   const int g = blockIdx.z;
@@ -326,7 +332,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_fp32_kernel(
     cur ^= 1;
   }
 
-  // D: col = lane&15, row = (lane>>4)*4 + rr
+  // D: col = lane&15, row = (lane>>4)*4 + rr. Atomic accumulate, or (DET)
+  // plain stores into this chunk's slot — every (chunk, k < Kg, col < RSC)
+  // has exactly one writer
+  float* dst = DET ? p.gw + (int64_t)chunk * p.pstride : p.gw;
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
@@ -337,7 +346,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_fp32_kernel(
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
         const int col = ntile * WF_BN + wn * 32 + ni * 16 + il;
-        if (col < p.RSC) atomicAdd(&p.gw[rowbase + col], acc[mi][ni][rr]);
+        if (col < p.RSC)
+          emit_partial<DET>(&dst[rowbase + col], acc[mi][ni][rr]);
       }
     }
   }
@@ -414,11 +424,28 @@ at::Tensor conv2d_wgrad_fp32(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
   p.chunks = (p.M + WF_CHUNK * WF_BK - 1) / (WF_CHUNK * WF_BK);
   p.magicHoWo = ((1ULL << 47) / ((unsigned long long)Ho * Wo)) + 1;
   p.magicWo = ((1ULL << 47) / (unsigned long long)Wo) + 1;
-  auto gwf = at::zeros({(int64_t)Kt, p.RSC}, x.options());
-  p.gw = gwf.data_ptr<float>();
+  const bool det = is_deterministic();  // sampled per launch
+  at::Tensor gwf, part;
+  if (det) {
+    gwf = at::empty({(int64_t)Kt, p.RSC}, x.options());
+    part = at::empty({(int64_t)p.chunks, (int64_t)Kt * p.RSC}, x.options());
+    p.gw = part.data_ptr<float>();
+    p.pstride = (int64_t)Kt * p.RSC;
+  } else {
+    gwf = at::zeros({(int64_t)Kt, p.RSC}, x.options());
+    p.gw = gwf.data_ptr<float>();
+    p.pstride = 0;
+  }
   dim3 grid(p.ktiles * p.ntiles, p.chunks, groups);
-  hipLaunchKernelGGL(conv_wgrad_fp32_kernel, grid, dim3(256), 0, cur_stream(),
-                     p);
+  if (det)
+    hipLaunchKernelGGL(conv_wgrad_fp32_kernel<true>, grid, dim3(256), 0,
+                       cur_stream(), p);
+  else
+    hipLaunchKernelGGL(conv_wgrad_fp32_kernel<false>, grid, dim3(256), 0,
+                       cur_stream(), p);
+  if (det)
+    ordered_reduce<float>(part.data_ptr<float>(), gwf.data_ptr<float>(),
+                          p.chunks, (int64_t)Kt * p.RSC, 1.f);
   // [Kt, RSC] rows are already [Kt][R][S][Cg] channels_last order
   return gwf.reshape({Kt, (int64_t)R, (int64_t)S, Cg})
       .permute({0, 3, 1, 2})

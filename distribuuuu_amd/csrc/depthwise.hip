@@ -95,8 +95,10 @@ __global__ void dwconv_dgrad_kernel(const T* __restrict__ gy,
 }
 
 // wgrad: per (c, r, s) reduce over pixels; block-local LDS tree then one
-// fp32 atomic per (c,r,s) per block.
-template <typename T>
+// fp32 atomic per (c,r,s) per block. DET (docs/DETERMINISM.md): gw is a
+// [gridDim.x][C*R*S] workspace and pixel-block blockIdx.x stores into its own
+// slot instead (every (c, r, s) of a slot has exactly one writer).
+template <typename T, bool DET>
 __global__ void dwconv_wgrad_kernel(const T* __restrict__ gy,
                                     const T* __restrict__ x,
                                     float* __restrict__ gw, int N, int H,
@@ -112,6 +114,7 @@ __global__ void dwconv_wgrad_kernel(const T* __restrict__ gy,
   const int64_t pixels = (int64_t)N * Ho * Wo;
   const int64_t p0 = (int64_t)blockIdx.x * pix_per_block;
   const int64_t p1 = min(p0 + pix_per_block, pixels);
+  float* gwb = DET ? gw + (int64_t)blockIdx.x * C * R * S : gw;
   const int ncp = min(cpacks, (int)blockDim.x);
   const int nrl = 1 << (31 - __builtin_clz((int)blockDim.x / ncp));
   const int cp0 = threadIdx.x % ncp;
@@ -154,7 +157,8 @@ __global__ void dwconv_wgrad_kernel(const T* __restrict__ gy,
     if (active && rl == 0) {
 #pragma unroll
       for (int j = 0; j < V; ++j)
-        atomicAdd(&gw[((int64_t)(cp * V + j) * R + r) * S + s], slot[j]);
+        emit_partial<DET>(
+            &gwb[((int64_t)(cp * V + j) * R + r) * S + s], slot[j]);
     }
     __syncthreads();
   }
@@ -218,26 +222,46 @@ at::Tensor dwconv_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
   check_nhwc(x, "x");
   const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int Ho = gy.size(2), Wo = gy.size(3);
-  auto acc = at::empty({C, 1, (int64_t)R, (int64_t)S},
-                       x.options().dtype(at::kFloat));
-  hipMemsetAsync(acc.data_ptr(), 0, acc.numel() * 4, cur_stream());
   const int64_t pixels = (int64_t)N * Ho * Wo;
+  const bool det = is_deterministic();  // sampled per launch
+  const int64_t n = (int64_t)C * R * S;
+  // [C,1,R,S]: contiguous and channels_last share one physical layout; the
+  // strides are those the atomic path returns (bf16: channels_last)
+  auto gw_opts = x.scalar_type() == at::kBFloat16
+                     ? x.options().memory_format(at::MemoryFormat::ChannelsLast)
+                     : x.options();
+  at::Tensor acc, out;
+  if (!det) {  // atomic mode: a zeroed [C,1,R,S] accumulator
+    acc = at::empty({C, 1, (int64_t)R, (int64_t)S},
+                    x.options().dtype(at::kFloat));
+    hipMemsetAsync(acc.data_ptr(), 0, acc.numel() * 4, cur_stream());
+  }
   DISPATCH_FLOAT_AND_BF16(x.scalar_type(), "dwconv_wgrad", [&] {
     constexpr int V = 16 / sizeof(scalar_t);
     const int cpacks = C / V;
     const int nrl = std::max(256 / std::min(cpacks, 256), 1);
     int64_t ppb = std::max<int64_t>(ceil_div(pixels, 256), nrl);
     int grid = (int)ceil_div(pixels, ppb);
-    hipLaunchKernelGGL((dwconv_wgrad_kernel<scalar_t>),
-                       dim3(grid, R * S), dim3(256), 0, cur_stream(),
+    // the grid is the same in both modes; only the accumulator differs.
+    // Deterministic: one slot per pixel block (<= 256), written in full, so
+    // no memset
+    if (det)
+      acc = at::empty({(int64_t)grid, n}, x.options().dtype(at::kFloat));
+    auto kern = det ? dwconv_wgrad_kernel<scalar_t, true>
+                    : dwconv_wgrad_kernel<scalar_t, false>;
+    hipLaunchKernelGGL(kern, dim3(grid, R * S), dim3(256), 0, cur_stream(),
                        (const scalar_t*)gy.data_ptr(),
                        (const scalar_t*)x.data_ptr(), acc.data_ptr<float>(),
                        N, H, W, C, Ho, Wo, R, S, sh, sw, ph, pw, ppb);
+    if (det) {
+      out = at::empty({C, 1, (int64_t)R, (int64_t)S}, gw_opts);
+      ordered_reduce<scalar_t>(acc.data_ptr<float>(),
+                               (scalar_t*)out.data_ptr(), grid, n, 1.f);
+    }
   });
+  if (det) return out.contiguous(at::MemoryFormat::ChannelsLast);
   if (x.scalar_type() == at::kBFloat16) {
-    auto gw = at::empty({C, 1, (int64_t)R, (int64_t)S},
-                        x.options().memory_format(at::MemoryFormat::ChannelsLast));
-    int64_t n = acc.numel();
+    auto gw = at::empty({C, 1, (int64_t)R, (int64_t)S}, gw_opts);
     hipLaunchKernelGGL(cast_f32_kernel, dim3(grid_1d(n, 256)), dim3(256), 0,
                        cur_stream(), acc.data_ptr<float>(),
                        (__hip_bfloat16*)gw.data_ptr(), n);

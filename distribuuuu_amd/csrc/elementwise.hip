@@ -157,8 +157,10 @@ __global__ __launch_bounds__(256) void se_scale_fwd_kernel(
 }
 
 // gs accumulates with fp32 atomics across row-chunk blocks (same
-// determinism tradeoff as the split-m wgrad; ~1e-3 relative run-to-run)
-template <typename T>
+// determinism tradeoff as the split-m wgrad; ~1e-3 relative run-to-run).
+// DET (docs/DETERMINISM.md): gs is a [gridDim.x][N*C] workspace and HW-chunk
+// blockIdx.x stores into its own slot (one writer per (n, c) of a slot).
+template <typename T, bool DET>
 __global__ __launch_bounds__(256) void se_scale_bwd_kernel(
     const T* __restrict__ gy, const T* __restrict__ x,
     const T* __restrict__ s, T* __restrict__ gx, float* __restrict__ gs,
@@ -179,7 +181,8 @@ __global__ __launch_bounds__(256) void se_scale_bwd_kernel(
   const P* xp = reinterpret_cast<const P*>(x) + (int64_t)n * HW * cpacks;
   P* oxp = reinterpret_cast<P*>(gx) + (int64_t)n * HW * cpacks;
   const P* sp = reinterpret_cast<const P*>(s) + (int64_t)n * cpacks;
-  float* gsp = gs + (int64_t)n * C;
+  float* gsp = gs + (int64_t)n * C +
+               (DET ? (int64_t)blockIdx.x * gridDim.y * C : 0);
   for (int cp = cp0; cp < cpacks; cp += ncp) {
     float acc[V] = {};
     if (active) {
@@ -221,7 +224,7 @@ __global__ __launch_bounds__(256) void se_scale_bwd_kernel(
     if (active && rl == 0) {
 #pragma unroll
       for (int j = 0; j < V; ++j)
-        atomicAdd(&gsp[cp * V + j], slot[j]);
+        emit_partial<DET>(&gsp[cp * V + j], slot[j]);
     }
     __syncthreads();
   }
@@ -256,22 +259,40 @@ std::vector<at::Tensor> se_scale_bwd(at::Tensor gy, at::Tensor x,
   const int N = x.size(0), C = x.size(1);
   const int HW = x.size(2) * x.size(3);
   auto gx = at::empty_like(x);
-  auto gsf = at::empty({N, C}, x.options().dtype(at::kFloat));
-  hipMemsetAsync(gsf.data_ptr(), 0, gsf.numel() * 4, cur_stream());
   const int chunks = std::max<int>(1, (int)ceil_div(768, N));
   const int rpc = (int)ceil_div(HW, chunks);
+  const int nchunk = (int)ceil_div(HW, rpc);
+  const bool det = is_deterministic();  // sampled per launch
+  // the grid is the same in both modes; only the accumulator differs: a
+  // zeroed [N, C], or one slot per HW-chunk (<= ceil(768/N)), written in
+  // full, so no memset
+  at::Tensor gsf, gs;
+  if (det) {
+    gsf = at::empty({(int64_t)nchunk, (int64_t)N * C},
+                    x.options().dtype(at::kFloat));
+    gs = at::empty({N, C}, x.options());
+  } else {
+    gsf = at::empty({N, C}, x.options().dtype(at::kFloat));
+    hipMemsetAsync(gsf.data_ptr(), 0, gsf.numel() * 4, cur_stream());
+  }
   DISPATCH_FLOAT_AND_BF16(x.scalar_type(), "se_scale_bwd", [&] {
     constexpr int V = 16 / sizeof(scalar_t);
     TORCH_CHECK(C % V == 0, "se_scale: C % ", V);
-    hipLaunchKernelGGL((se_scale_bwd_kernel<scalar_t>),
-                       dim3((int)ceil_div(HW, rpc), N), dim3(256), 0,
-                       cur_stream(), (const scalar_t*)gy.data_ptr(),
+    auto kern = det ? se_scale_bwd_kernel<scalar_t, true>
+                    : se_scale_bwd_kernel<scalar_t, false>;
+    hipLaunchKernelGGL(kern, dim3(nchunk, N), dim3(256), 0, cur_stream(),
+                       (const scalar_t*)gy.data_ptr(),
                        (const scalar_t*)x.data_ptr(),
                        (const scalar_t*)s.data_ptr(),
-                       (scalar_t*)gx.data_ptr(), gsf.data_ptr<float>(),
-                       HW, C, rpc);
+                       (scalar_t*)gx.data_ptr(), gsf.data_ptr<float>(), HW, C,
+                       rpc);
+    if (det)
+      ordered_reduce<scalar_t>(gsf.data_ptr<float>(),
+                               (scalar_t*)gs.data_ptr(), nchunk,
+                               (int64_t)N * C, 1.f);
   });
-  return {gx, gsf.to(x.scalar_type()).reshape({N, C, 1, 1})};
+  if (!det) gs = gsf.to(x.scalar_type());
+  return {gx, gs.reshape({N, C, 1, 1})};
 }
 
 // ---------------------------------------------------------------------------

@@ -1,10 +1,13 @@
 // Cross-entropy loss and top-k accuracy (K15).
 // ce_fwd: one block per row; block-reduce max, sum-exp; mean loss via one
-// fp32 atomic per row. ce_bwd: gx = gl * (softmax - onehot) / N.
+// fp32 atomic per row (deterministic mode, docs/DETERMINISM.md: per-row
+// losses stored to a [N] buffer and summed in row order by ordered_reduce).
+// ce_bwd: gx = gl * (softmax - onehot) / N.
 #include "common.h"
 
 namespace {
 
+template <bool DET>
 __global__ void ce_fwd_kernel(const float* __restrict__ logits,
                               const int64_t* __restrict__ target,
                               float* __restrict__ loss,
@@ -22,7 +25,8 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits,
   const float l = m + __logf(s);
   if (threadIdx.x == 0) {
     lse[n] = l;
-    atomicAdd(loss, (l - row[target[n]]) / N);
+    // DET: loss is the [N] per-row buffer
+    emit_partial<DET>(DET ? loss + n : loss, (l - row[target[n]]) / N);
   }
 }
 
@@ -74,11 +78,23 @@ std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target) {
   CHECK_GPU(logits);
   TORCH_CHECK(logits.scalar_type() == at::kFloat, "ce_fwd expects fp32 logits");
   const int N = logits.size(0), K = logits.size(1);
-  auto loss = at::zeros({}, logits.options());
   auto lse = at::empty({N}, logits.options());
-  hipLaunchKernelGGL(ce_fwd_kernel, dim3(N), dim3(256), 0, cur_stream(),
-                     logits.data_ptr<float>(), target.data_ptr<int64_t>(),
-                     loss.data_ptr<float>(), lse.data_ptr<float>(), N, K);
+  if (is_deterministic()) {  // sampled per launch
+    auto rowloss = at::empty({N}, logits.options());
+    auto loss = at::empty({}, logits.options());
+    hipLaunchKernelGGL(ce_fwd_kernel<true>, dim3(N), dim3(256), 0,
+                       cur_stream(), logits.data_ptr<float>(),
+                       target.data_ptr<int64_t>(), rowloss.data_ptr<float>(),
+                       lse.data_ptr<float>(), N, K);
+    ordered_reduce<float>(rowloss.data_ptr<float>(), loss.data_ptr<float>(), N,
+                          1, 1.f);
+    return {loss, lse};
+  }
+  auto loss = at::zeros({}, logits.options());
+  hipLaunchKernelGGL(ce_fwd_kernel<false>, dim3(N), dim3(256), 0,
+                     cur_stream(), logits.data_ptr<float>(),
+                     target.data_ptr<int64_t>(), loss.data_ptr<float>(),
+                     lse.data_ptr<float>(), N, K);
   return {loss, lse};
 }
 

@@ -13,6 +13,9 @@
 //
 // Split-m: each block owns a pixel chunk and atomically accumulates its fp32
 // partial tile into gw_accum[Kt][R*S*Cg]; a final cast kernel emits bf16.
+// Deterministic mode (docs/DETERMINISM.md): each block instead stores its
+// partial into slot `chunk` of a [chunks][Kt*R*S*Cg] workspace and
+// ordered_reduce (det_reduce.hip) sums the slots in order and emits bf16.
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4w;
@@ -32,7 +35,7 @@ constexpr int TILE_BYTES = 8 * SUBT;  // 2 m-subtiles x 4 col-subtiles
 struct WgradParams {
   const __hip_bfloat16* x;   // [N,H,W,Ct]
   const __hip_bfloat16* gy;  // [N,Ho,Wo,Kt]
-  float* acc;                // [Kt, R*S*Cg] zeroed
+  float* acc;                // [Kt, R*S*Cg] zeroed, or part[chunks][pstride]
   int N, H, W, Ct, Kt;
   int R, S, Cg, Kg;
   int sh, sw, ph, pw, dh, dw;
@@ -43,6 +46,8 @@ struct WgradParams {
   // m*d < 2^47 (here m < 2^22, d < 2^15). Runtime u32 division in the
   // per-k-step staging path costs ~30 VALU cycles each.
   unsigned long long magicHoWo, magicWo;
+  // last, so every other kernarg keeps its offset
+  int64_t pstride;  // DET kernels: workspace slot stride (Kt*RSC)
 };
 
 DEV_INLINE int magic_div(int m, unsigned long long magic) {
@@ -102,6 +107,7 @@ DEV_INLINE void tr_read_issue(unsigned a0, unsigned a1, TrFrag& f) {
       : "memory");
 }
 
+template <bool DET>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradParams p) {
   const int g = blockIdx.z;
   int ktile, ntile, chunk;
@@ -246,7 +252,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradParams p) {
     cur ^= 1;
   }
 
-  // epilogue: fp32 atomic accumulate (D: col=lane&15, row=(lane>>4)*4+rr)
+  // epilogue (D: col=lane&15, row=(lane>>4)*4+rr): fp32 atomic accumulate,
+  // or (DET) plain stores into this chunk's own workspace slot — every
+  // (chunk, k < Kg, col < RSC) has exactly one writer
+  float* dst = DET ? p.acc + (int64_t)chunk * p.pstride : p.acc;
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
@@ -257,7 +266,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradParams p) {
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
         const int col = ntile * WBN + wn * 32 + ni * 16 + il;
-        if (col < p.RSC) atomicAdd(&p.acc[rowbase + col], accv[mi][ni][rr]);
+        if (col < p.RSC)
+          emit_partial<DET>(&dst[rowbase + col], accv[mi][ni][rr]);
       }
     }
   }
@@ -278,7 +288,7 @@ constexpr int T128_TILE = 16 * SUBT;    // one operand tile (16.5 KB)
 struct WgradT128Params {
   const __hip_bfloat16* x;   // [N,H,W,Ct]
   const __hip_bfloat16* gy;  // [N,Ho,Wo,Kt]
-  float* acc;                // [Kt, R*S*Cg] zeroed
+  float* acc;                // [Kt, R*S*Cg] zeroed, or part[chunks][pstride]
   int N, H, W, Ct, Kt;
   int R, S, Cg, Kg;
   int sh, sw, ph, pw, dh, dw;
@@ -287,8 +297,11 @@ struct WgradT128Params {
   int ktiles, ntiles, chunks, csteps;
   int xcd_remap;
   unsigned long long magicHoWo, magicWo;
+  // last, so every other kernarg keeps its offset
+  int64_t pstride;  // DET kernels: workspace slot stride (Kt*RSC)
 };
 
+template <bool DET>
 __global__ __launch_bounds__(256) void conv_wgrad_tr128_kernel(
     WgradT128Params p) {
   const int g = blockIdx.z;
@@ -455,7 +468,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_tr128_kernel(
     cur ^= 1;
   }
 
-  // epilogue: fp32 atomic accumulate (D: col=lane&15, row=(lane>>4)*4+rr)
+  // epilogue (D: col=lane&15, row=(lane>>4)*4+rr): fp32 atomic accumulate,
+  // or (DET) plain stores into this chunk's own workspace slot — every
+  // (chunk, k < Kg, col < RSC) has exactly one writer
+  float* dst = DET ? p.acc + (int64_t)chunk * p.pstride : p.acc;
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
@@ -466,7 +482,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_tr128_kernel(
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const int col = ntile * T128_BN + wn * 64 + ni * 16 + il;
-        if (col < p.RSC) atomicAdd(&p.acc[rowbase + col], accv[mi][ni][rr]);
+        if (col < p.RSC)
+          emit_partial<DET>(&dst[rowbase + col], accv[mi][ni][rr]);
       }
     }
   }
@@ -487,17 +504,20 @@ constexpr int RSLOT = 2 * RTILE;          // A + B per ring slot (16 KB)
 struct WgradRingParams {
   const __hip_bfloat16* x;   // padded [N, Hp, Wp, Ct] when ph/pw > 0
   const __hip_bfloat16* gy;  // [M, Kt]
-  float* acc;                // [Kt, R*S*Cg] zeroed
+  float* acc;                // [Kt, R*S*Cg] zeroed, or part[chunks][pstride]
   int Hp, Wp, Ct, Kt;
   int R, S, Cg, Kg;
   int sh, sw, dh, dw;
   int Ho, Wo;
   int M, RSC;
   int ktiles, ntiles;
+  // last, so every other kernarg keeps its offset
+  int64_t pstride;  // DET kernels: workspace slot stride (Kt*RSC)
 };
 
 #define RWAITVM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
 
+template <bool DET>
 __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(
     WgradRingParams p) {
   const int g = blockIdx.z;
@@ -633,7 +653,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(
     bufsel = bufsel == 2 ? 0 : bufsel + 1;
   }
 
-  // epilogue: fp32 atomic accumulate (D: col=lane&15, row=(lane>>4)*4+rr)
+  // epilogue (D: col=lane&15, row=(lane>>4)*4+rr): fp32 atomic accumulate,
+  // or (DET) plain stores into this chunk's own workspace slot — every
+  // (chunk, k < Kg, col < RSC) has exactly one writer
+  float* dst = DET ? p.acc + (int64_t)chunk * p.pstride : p.acc;
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
@@ -644,7 +667,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
         const int col = ntile * WBN + wn * 32 + ni * 16 + il;
-        if (col < p.RSC) atomicAdd(&p.acc[rowbase + col], accv[mi][ni][rr]);
+        if (col < p.RSC)
+          emit_partial<DET>(&dst[rowbase + col], accv[mi][ni][rr]);
       }
     }
   }
@@ -668,7 +692,7 @@ constexpr int R128_SLOT = 2 * R128_TILE;
 struct Wgrad128Params {
   const __hip_bfloat16* x;   // padded [N, Hp, Wp, Ct] when ph/pw > 0
   const __hip_bfloat16* gy;  // [M, Kt]
-  float* acc;                // [Kt, R*S*Cg] zeroed
+  float* acc;                // [Kt, R*S*Cg] zeroed, or part[chunks][pstride]
   int Hp, Wp, Ct, Kt;
   int R, S, Cg, Kg;
   int sh, sw, dh, dw;
@@ -676,8 +700,11 @@ struct Wgrad128Params {
   int M, RSC;
   int ktiles, ntiles, csteps;
   unsigned long long magicHoWo, magicWo;
+  // last, so every other kernarg keeps its offset
+  int64_t pstride;  // DET kernels: workspace slot stride (Kt*RSC)
 };
 
+template <bool DET>
 __global__ __launch_bounds__(256) void conv_wgrad_ring128_kernel(
     Wgrad128Params p) {
   extern __shared__ __align__(16) char smem[];  // 3 * R128_SLOT
@@ -820,7 +847,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_ring128_kernel(
     bufsel = bufsel == 2 ? 0 : bufsel + 1;
   }
 
-  // epilogue: fp32 atomic accumulate (D: col=lane&15, row=(lane>>4)*4+rr)
+  // epilogue (D: col=lane&15, row=(lane>>4)*4+rr): fp32 atomic accumulate,
+  // or (DET) plain stores into this chunk's own workspace slot — every
+  // (chunk, k < Kg, col < RSC) has exactly one writer
+  float* dst = DET ? p.acc + (int64_t)chunk * p.pstride : p.acc;
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
@@ -831,7 +861,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_ring128_kernel(
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const int col = ntile * R128_BN + wn * 64 + ni * 16 + il;
-        if (col < p.RSC) atomicAdd(&p.acc[rowbase + col], accv[mi][ni][rr]);
+        if (col < p.RSC)
+          emit_partial<DET>(&dst[rowbase + col], accv[mi][ni][rr]);
       }
     }
   }
@@ -870,6 +901,56 @@ __global__ void cast_acc_kernel(const float* __restrict__ acc,
     gw[i] = from_f32<__hip_bfloat16>(acc[i]);
 }
 
+// Deterministic-mode workspace cap for the kernels whose split-m chunk is a
+// runtime value (tr128, ring128): their csteps grows until
+// chunks * Kt * RSC * 4 bytes fits (or one chunk is left).
+constexpr int64_t DET_WS_CAP = (int64_t)64 << 20;
+
+int det_grow_csteps(int csteps, int64_t M64, int64_t slot_elems) {
+  auto nchunks = [&](int cs) {
+    return (M64 + (int64_t)cs * WBK - 1) / ((int64_t)cs * WBK);
+  };
+  while (nchunks(csteps) > 1 && nchunks(csteps) * slot_elems * 4 > DET_WS_CAP)
+    csteps *= 2;
+  return csteps;
+}
+
+// fp32 accumulator of one wgrad launch: a zeroed [Kt, RSC] buffer for the
+// atomic epilogue, or in deterministic mode a [chunks][Kt*RSC] workspace
+// (no memset: every slot is written in full). Both come from the caching
+// allocator, so they are safe on the wgrad side stream and under capture.
+at::Tensor wg_acc_alloc(const at::Tensor& x, int64_t Kt, int64_t RSC,
+                        int64_t chunks, bool det, int64_t* pstride) {
+  auto opts = x.options().dtype(at::kFloat);
+  if (det) {
+    *pstride = Kt * RSC;
+    return at::empty({chunks, Kt * RSC}, opts);
+  }
+  *pstride = 0;
+  auto acc = at::empty({Kt, RSC}, opts);
+  hipMemsetAsync(acc.data_ptr(), 0, acc.numel() * 4, cur_stream());
+  return acc;
+}
+
+// bf16 gw from the accumulator: cast pass (atomic mode) or the ordered
+// reduction over chunks, which emits bf16 itself (deterministic mode)
+at::Tensor wg_emit_gw(const at::Tensor& x, const at::Tensor& acc, int64_t Kt,
+                      int64_t Cg, int64_t R, int64_t S, int64_t chunks,
+                      bool det) {
+  auto gw = at::empty({Kt, Cg, R, S},
+                      x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  const int64_t total = Kt * R * S * Cg;
+  if (det)
+    ordered_reduce<__hip_bfloat16>(acc.data_ptr<float>(),
+                                   (__hip_bfloat16*)gw.data_ptr(), (int)chunks,
+                                   total, 1.f);
+  else
+    hipLaunchKernelGGL(cast_acc_kernel, dim3(grid_1d(total, 256)), dim3(256),
+                       0, cur_stream(), acc.data_ptr<float>(),
+                       (__hip_bfloat16*)gw.data_ptr(), total);
+  return gw;
+}
+
 }  // namespace
 
 at::Tensor conv2d_wgrad_fp32(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
@@ -890,6 +971,7 @@ at::Tensor conv2d_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
   const int Cg = Ct / groups, Kg = Kt / groups;
   TORCH_CHECK(Cg % 8 == 0 && Kg % 8 == 0, "wgrad: Cg/Kg must be multiples of 8");
   const int64_t M64 = (int64_t)N * Ho * Wo;
+  const bool det = is_deterministic();  // sampled per launch
   const bool ring_ok = (M64 % 64 == 0) && (Kg % 64 == 0) &&
                        ((S * Cg) % 64 == 0) && (Cg % 8 == 0) &&
                        ((R * S * Cg) % 16 == 0);
@@ -924,19 +1006,16 @@ at::Tensor conv2d_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
     q.ktiles = Kg / WBM;
     q.ntiles = (q.RSC + WBN - 1) / WBN;
     const int chunks = (int)((M64 + CHUNK_STEPS * WBK - 1) / (CHUNK_STEPS * WBK));
-    auto accbuf2 = at::empty({(int64_t)Kt, q.RSC}, x.options().dtype(at::kFloat));
-    hipMemsetAsync(accbuf2.data_ptr(), 0, accbuf2.numel() * 4, cur_stream());
+    auto accbuf2 = wg_acc_alloc(x, Kt, q.RSC, chunks, det, &q.pstride);
     q.acc = accbuf2.data_ptr<float>();
     dim3 grid2(q.ktiles * q.ntiles, chunks, groups);
-    hipLaunchKernelGGL(conv_wgrad_ring_kernel, grid2, dim3(256), 0,
-                       cur_stream(), q);
-    auto gw2 = at::empty({Kt, Cg, (int64_t)R, (int64_t)S},
-                         x.options().memory_format(at::MemoryFormat::ChannelsLast));
-    const int64_t total2 = (int64_t)Kt * q.RSC;
-    hipLaunchKernelGGL(cast_acc_kernel, dim3(grid_1d(total2, 256)), dim3(256),
-                       0, cur_stream(), q.acc,
-                       (__hip_bfloat16*)gw2.data_ptr(), total2);
-    return gw2;
+    if (det)
+      hipLaunchKernelGGL(conv_wgrad_ring_kernel<true>, grid2, dim3(256), 0,
+                         cur_stream(), q);
+    else
+      hipLaunchKernelGGL(conv_wgrad_ring_kernel<false>, grid2, dim3(256), 0,
+                         cur_stream(), q);
+    return wg_emit_gw(x, accbuf2, Kt, Cg, R, S, chunks, det);
   }
 
   // 128x128 ring kernel where it measured faster (tools/probes/convmap.py):
@@ -996,28 +1075,31 @@ at::Tensor conv2d_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
       csteps /= 2;
       chunks = (int)((M64 + (int64_t)csteps * WBK - 1) / (csteps * WBK));
     }
+    if (det) {  // bound the workspace (DET_WS_CAP)
+      csteps = det_grow_csteps(csteps, M64, (int64_t)Kt * q.RSC);
+      chunks = (int)((M64 + (int64_t)csteps * WBK - 1) / (csteps * WBK));
+    }
     q.csteps = csteps;
-    auto accbuf = at::empty({(int64_t)Kt, q.RSC},
-                            x.options().dtype(at::kFloat));
-    hipMemsetAsync(accbuf.data_ptr(), 0, accbuf.numel() * 4, cur_stream());
+    auto accbuf = wg_acc_alloc(x, Kt, q.RSC, chunks, det, &q.pstride);
     q.acc = accbuf.data_ptr<float>();
     static bool attr_done = false;
     if (!attr_done) {
-      hipFuncSetAttribute((const void*)conv_wgrad_ring128_kernel,
+      hipFuncSetAttribute((const void*)conv_wgrad_ring128_kernel<false>,
+                          hipFuncAttributeMaxDynamicSharedMemorySize,
+                          3 * R128_SLOT);
+      hipFuncSetAttribute((const void*)conv_wgrad_ring128_kernel<true>,
                           hipFuncAttributeMaxDynamicSharedMemorySize,
                           3 * R128_SLOT);
       attr_done = true;
     }
     dim3 grid(q.ktiles * q.ntiles, chunks, groups);
-    hipLaunchKernelGGL(conv_wgrad_ring128_kernel, grid, dim3(256),
-                       3 * R128_SLOT, cur_stream(), q);
-    auto gw = at::empty({Kt, Cg, (int64_t)R, (int64_t)S},
-                        x.options().memory_format(at::MemoryFormat::ChannelsLast));
-    const int64_t total = (int64_t)Kt * q.RSC;
-    hipLaunchKernelGGL(cast_acc_kernel, dim3(grid_1d(total, 256)), dim3(256),
-                       0, cur_stream(), q.acc, (__hip_bfloat16*)gw.data_ptr(),
-                       total);
-    return gw;
+    if (det)
+      hipLaunchKernelGGL(conv_wgrad_ring128_kernel<true>, grid, dim3(256),
+                         3 * R128_SLOT, cur_stream(), q);
+    else
+      hipLaunchKernelGGL(conv_wgrad_ring128_kernel<false>, grid, dim3(256),
+                         3 * R128_SLOT, cur_stream(), q);
+    return wg_emit_gw(x, accbuf, Kt, Cg, R, S, chunks, det);
   }
 
   // 128x128 tr-staged tile (A/B via DISTRIBUUUU_WGRAD_T128: 1 force,
@@ -1056,23 +1138,22 @@ at::Tensor conv2d_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
         csteps /= 2;
         chunks = (int)((M64 + (int64_t)csteps * WBK - 1) / (csteps * WBK));
       }
+      if (det) {  // bound the workspace (DET_WS_CAP)
+        csteps = det_grow_csteps(csteps, M64, (int64_t)Kt * q.RSC);
+        chunks = (int)((M64 + (int64_t)csteps * WBK - 1) / (csteps * WBK));
+      }
       q.csteps = csteps;
       q.chunks = chunks;
-      auto accb = at::empty({(int64_t)Kt, q.RSC},
-                            x.options().dtype(at::kFloat));
-      hipMemsetAsync(accb.data_ptr(), 0, accb.numel() * 4, cur_stream());
+      auto accb = wg_acc_alloc(x, Kt, q.RSC, chunks, det, &q.pstride);
       q.acc = accb.data_ptr<float>();
       dim3 grid(q.ktiles * q.ntiles, chunks, groups);
-      hipLaunchKernelGGL(conv_wgrad_tr128_kernel, grid, dim3(256), 0,
-                         cur_stream(), q);
-      auto gw = at::empty({Kt, Cg, (int64_t)R, (int64_t)S},
-                          x.options().memory_format(
-                              at::MemoryFormat::ChannelsLast));
-      const int64_t tot = (int64_t)Kt * q.RSC;
-      hipLaunchKernelGGL(cast_acc_kernel, dim3(grid_1d(tot, 256)), dim3(256),
-                         0, cur_stream(), q.acc,
-                         (__hip_bfloat16*)gw.data_ptr(), tot);
-      return gw;
+      if (det)
+        hipLaunchKernelGGL(conv_wgrad_tr128_kernel<true>, grid, dim3(256), 0,
+                           cur_stream(), q);
+      else
+        hipLaunchKernelGGL(conv_wgrad_tr128_kernel<false>, grid, dim3(256), 0,
+                           cur_stream(), q);
+      return wg_emit_gw(x, accb, Kt, Cg, R, S, chunks, det);
     }
     (void)t128_blocks;
   }
@@ -1092,19 +1173,16 @@ at::Tensor conv2d_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
   p.magicHoWo = ((1ULL << 47) / ((unsigned long long)Ho * Wo)) + 1;
   p.magicWo = ((1ULL << 47) / (unsigned long long)Wo) + 1;
 
-  auto accbuf = at::empty({(int64_t)Kt, p.RSC}, x.options().dtype(at::kFloat));
-  hipMemsetAsync(accbuf.data_ptr(), 0, accbuf.numel() * 4, cur_stream());
+  auto accbuf = wg_acc_alloc(x, Kt, p.RSC, p.chunks, det, &p.pstride);
   p.acc = accbuf.data_ptr<float>();
   dim3 grid(p.ktiles * p.ntiles, p.chunks, groups);
   if (p.ktiles * p.ntiles <= 12)  // XCD-grouped 1-D grid (see kernel)
     grid = dim3(p.ktiles * p.ntiles * ((p.chunks + 7) / 8 * 8), 1, groups);
-  hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 0, cur_stream(), p);
-
-  auto gw = at::empty({Kt, Cg, (int64_t)R, (int64_t)S},
-                      x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const int64_t total = (int64_t)Kt * p.RSC;
-  hipLaunchKernelGGL(cast_acc_kernel, dim3(grid_1d(total, 256)), dim3(256), 0,
-                     cur_stream(), p.acc, (__hip_bfloat16*)gw.data_ptr(),
-                     total);
-  return gw;
+  if (det)
+    hipLaunchKernelGGL(conv_wgrad_kernel<true>, grid, dim3(256), 0,
+                       cur_stream(), p);
+  else
+    hipLaunchKernelGGL(conv_wgrad_kernel<false>, grid, dim3(256), 0,
+                       cur_stream(), p);
+  return wg_emit_gw(x, accbuf, Kt, Cg, R, S, p.chunks, det);
 }

@@ -9,7 +9,13 @@ The extension is REQUIRED on a GPU machine: if a CUDA/ROCm device is visible and
 extension is missing, op calls raise instead of silently falling back to ATen.
 """
 
-from .dispatch import ext, hip_op_available, require_ext  # noqa: F401
+from .dispatch import (  # noqa: F401
+    ext,
+    hip_op_available,
+    is_deterministic,
+    require_ext,
+    set_deterministic,
+)
 from .modules import (  # noqa: F401
     AdaptiveAvgPool2d,
     AvgPool2d,

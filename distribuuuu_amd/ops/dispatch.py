@@ -52,6 +52,38 @@ def require_ext():
     return e
 
 
+# ---------------------------------------------------------------------------
+# Deterministic mode (docs/DETERMINISM.md)
+# ---------------------------------------------------------------------------
+# Python-side copy of the extension's process-global flag, so the switch also
+# works on a CPU-only box where ext() is None. Same initial value and the same
+# rule as the extension (det_reduce.hip): exactly "1" turns it on.
+_DETERMINISTIC = os.environ.get("DISTRIBUUUU_DETERMINISTIC", "0") == "1"
+
+
+def set_deterministic(flag):
+    """Switch the cross-block reductions of the HIP kernels (conv/depthwise
+    wgrad, SE-scale backward, MHSA relative-position grads, the mean loss)
+    between fp32 atomics (False, the fast default) and ordered workspace
+    reductions that repeat bit for bit (True).
+
+    The flag is sampled when a kernel is launched: a captured hipGraph keeps
+    the mode it was captured in.
+    """
+    global _DETERMINISTIC
+    _DETERMINISTIC = bool(flag)
+    e = ext()
+    if e is not None:
+        e.set_deterministic(_DETERMINISTIC)
+
+
+def is_deterministic():
+    e = ext()
+    if e is not None:
+        return bool(e.is_deterministic())
+    return _DETERMINISTIC
+
+
 def hip_op_available(name):
     if os.environ.get("DISTRIBUUUU_FORCE_TORCH", "0") == "1":
         return False

@@ -88,7 +88,15 @@ def get_world_size():
 # Seeding / determinism (reference utils.py:54-68)
 # ---------------------------------------------------------------------------
 def setup_seed(rank=0):
-    """Rank 0 creates OUT_DIR and dumps the config; seed with RNG_SEED+rank."""
+    """Rank 0 creates OUT_DIR and dumps the config; seed with RNG_SEED+rank.
+
+    CUDNN.DETERMINISTIC is the one switch of the HIP kernels' deterministic
+    mode (docs/DETERMINISM.md); RNG_SEED alone seeds and keeps the fast
+    atomic kernels. A bit-reproducible run sets both.
+    """
+    from . import ops
+
+    ops.set_deterministic(bool(cfg.CUDNN.DETERMINISTIC))
     if rank == 0:
         os.makedirs(cfg.OUT_DIR, exist_ok=True)
         dump_cfg()

@@ -1,8 +1,10 @@
 """Per-kernel micro-benchmarks on representative ResNet-50 shapes.
 
-Usage (on a GPU box): python tools/kbench.py [group ...]
+Usage (on a GPU box): python tools/kbench.py [--deterministic] [group ...]
 Groups: bn conv wgrad pool ce sgd all
 Prints achieved GB/s (memory-bound ops) or TF/s (MFMA ops) per shape.
+--deterministic: the wgrad rows time each shape in both modes, atomic and
+deterministic (docs/DETERMINISM.md), side by side.
 """
 
 import sys
@@ -99,8 +101,11 @@ def bench_conv():
         print(line)
 
 
-def bench_wgrad():
-    print("== conv wgrad (TF/s) ==")
+def bench_wgrad(deterministic=False):
+    from distribuuuu_amd import ops
+
+    print("== conv wgrad (TF/s) ==" if not deterministic else
+          "== conv wgrad, atomic vs deterministic (TF/s) ==")
     for shp in CONV_SHAPES:
         n, c, h, w, k, r, s = shp
         cc = 8 if c < 8 else c
@@ -110,7 +115,17 @@ def bench_wgrad():
         gy = _cl(torch.randn(n, k, ho, ho, device=DEV, dtype=torch.bfloat16))
         flops = 2.0 * n * ho * ho * k * cc * r * r
         t = timeit(lambda: e.conv2d_wgrad(gy, x, r, r, s, s, p, p, 1, 1, 1))
-        print(f"wgrad {str(shp):26s} {t*1e6:8.1f} us  {flops/t/1e12:6.1f} TF")
+        line = f"wgrad {str(shp):26s} {t*1e6:8.1f} us  {flops/t/1e12:6.1f} TF"
+        if deterministic:
+            ops.set_deterministic(True)
+            try:
+                td = timeit(
+                    lambda: e.conv2d_wgrad(gy, x, r, r, s, s, p, p, 1, 1, 1))
+            finally:
+                ops.set_deterministic(False)
+            line += (f" | det {td*1e6:8.1f} us {flops/td/1e12:6.1f} TF"
+                     f"  x{td/t:4.2f}")
+        print(line)
 
 
 def bench_pool():
@@ -138,13 +153,15 @@ def bench_gemm():
 
 
 if __name__ == "__main__":
-    groups = sys.argv[1:] or ["all"]
+    args = sys.argv[1:]
+    deterministic = "--deterministic" in args
+    groups = [a for a in args if a != "--deterministic"] or ["all"]
     if "bn" in groups or "all" in groups:
         bench_bn()
     if "conv" in groups or "all" in groups:
         bench_conv()
     if "wgrad" in groups or "all" in groups:
-        bench_wgrad()
+        bench_wgrad(deterministic)
     if "pool" in groups or "all" in groups:
         bench_pool()
     if "gemm" in groups or "all" in groups:
