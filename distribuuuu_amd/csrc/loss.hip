@@ -3,6 +3,11 @@
 // fp32 atomic per row (deterministic mode, docs/DETERMINISM.md: per-row
 // losses stored to a [N] buffer and summed in row order by ordered_reduce).
 // ce_bwd: gx = gl * (softmax - onehot) / N.
+// The forward hands the backward the row max m and log(sum exp(x - m)) as a
+// PAIR ([N, 2]), never their sum: with logits near 100, m + log(sum) rounds at
+// ulp(128) = 1.5e-5, a relative error of that size in every probability of
+// the row (and a row of gradients that no longer sums to 0). Both kernels
+// work on x - m, which is small where it matters.
 #include "common.h"
 
 namespace {
@@ -20,13 +25,14 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits,
   m = block_reduce_max<true>(m, lds);
   __syncthreads();
   float s = 0.f;
-  for (int j = threadIdx.x; j < K; j += blockDim.x) s += __expf(row[j] - m);
+  for (int j = threadIdx.x; j < K; j += blockDim.x) s += expf(row[j] - m);
   s = block_reduce_sum<true>(s, lds);
-  const float l = m + __logf(s);
+  const float ls = logf(s);
   if (threadIdx.x == 0) {
-    lse[n] = l;
+    lse[2 * n] = m;
+    lse[2 * n + 1] = ls;
     // DET: loss is the [N] per-row buffer
-    emit_partial<DET>(DET ? loss + n : loss, (l - row[target[n]]) / N);
+    emit_partial<DET>(DET ? loss + n : loss, (ls - (row[target[n]] - m)) / N);
   }
 }
 
@@ -40,7 +46,7 @@ __global__ void ce_bwd_kernel(const float* __restrict__ logits,
        i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t n = i / K;
     const int j = i % K;
-    float p = __expf(logits[i] - lse[n]);
+    float p = expf((logits[i] - lse[2 * n]) - lse[2 * n + 1]);
     float t = (j == (int)target[n]) ? 1.f : 0.f;
     gx[i] = g * (p - t) / (total / K);
   }
@@ -78,7 +84,7 @@ std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target) {
   CHECK_GPU(logits);
   TORCH_CHECK(logits.scalar_type() == at::kFloat, "ce_fwd expects fp32 logits");
   const int N = logits.size(0), K = logits.size(1);
-  auto lse = at::empty({N}, logits.options());
+  auto lse = at::empty({N, 2}, logits.options());  // (max, log sum exp(x - max))
   if (is_deterministic()) {  // sampled per launch
     auto rowloss = at::empty({N}, logits.options());
     auto loss = at::empty({}, logits.options());
@@ -102,6 +108,9 @@ at::Tensor ce_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
                   at::Tensor gl) {
   CHECK_GPU(logits);
   const int N = logits.size(0), K = logits.size(1);
+  TORCH_CHECK(lse.dim() == 2 && lse.size(0) == N && lse.size(1) == 2 &&
+                  lse.is_contiguous() && lse.scalar_type() == at::kFloat,
+              "ce_bwd: lse must be ce_fwd's [N, 2] (max, log-sum) pairs");
   auto gx = at::empty_like(logits);
   int64_t total = (int64_t)N * K;
   hipLaunchKernelGGL(ce_bwd_kernel, dim3(grid_1d(total, 256)), dim3(256), 0,

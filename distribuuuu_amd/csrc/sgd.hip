@@ -7,7 +7,9 @@
 //
 // Table layout: int64 [nchunks, 6]:
 //   [grad_ptr, param_ptr, mom_ptr, master_ptr, offset, count | flags<<32]
-//   flags bit0: param bf16, bit1: grad bf16
+//   flags bit0: param bf16, bit1: grad bf16, bit2: momentum uninitialised
+//   (first step of this parameter: the buffer is seeded with the gradient,
+//   dampening not applied — torch.optim.SGD semantics)
 #include "common.h"
 
 namespace {
@@ -23,13 +25,14 @@ __global__ void sgd_kernel(const long long* __restrict__ recs, float lr,
   const int count = (int)(rec[5] & 0xffffffffll);
   const int flags = (int)(rec[5] >> 32);
   const bool p_bf16 = flags & 1, g_bf16 = flags & 2;
+  const float gscale = (flags & 4) ? 1.f : 1.f - damp;
   for (int i = threadIdx.x; i < count; i += blockDim.x) {
     const int64_t j = off + i;
     float g = g_bf16 ? to_f32(((const __hip_bfloat16*)grad)[j])
                      : ((const float*)grad)[j];
     float w = master[j];
     if (wd != 0.f) g += wd * w;
-    float m = mom[j] * mu + (1.f - damp) * g;
+    float m = mom[j] * mu + gscale * g;
     mom[j] = m;
     const float upd = nesterov ? g + mu * m : m;
     w -= lr * upd;

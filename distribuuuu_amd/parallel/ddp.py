@@ -20,6 +20,17 @@ import torch.distributed as dist
 import torch.nn as nn
 
 
+def _is_dense(t):
+    """Non-overlapping and dense: the strides address exactly numel() slots."""
+    expect = 1
+    for st, s in sorted((st, s) for s, st in zip(t.shape, t.stride())
+                        if s != 1):
+        if st != expect:
+            return False
+        expect *= s
+    return True
+
+
 class _Bucket:
     __slots__ = ("params", "buffer", "views", "pending", "work")
 
@@ -83,7 +94,12 @@ class DistributedDataParallel(nn.Module):
             b.buffer = torch.zeros(total, dtype=dtype, device=device)
             off = 0
             for p in b.params:
-                b.views[p] = b.buffer[off:off + p.numel()].view_as(p)
+                flat = b.buffer[off:off + p.numel()]
+                # the grad view takes the PARAMETER's strides (channels_last
+                # weights): autograd's layout contract, and the fused SGD
+                # kernel indexes grad and param by one storage offset
+                b.views[p] = (flat.as_strided(p.size(), p.stride())
+                              if _is_dense(p) else flat.view_as(p))
                 off += p.numel()
             b.pending = len(b.params)
         for b in self._buckets:

@@ -194,7 +194,10 @@ def test_topk_acc():
 
 
 @pytest.mark.parametrize("param_dtype", [torch.float32, torch.bfloat16])
-def test_sgd_step_matches_torch(param_dtype):
+def test_sgd_step_matches_fp32_formula(param_dtype):
+    """Nesterov + weight decay against the kernel's own formula written out in
+    fp32 tensor ops (constant lr, constant grads). The comparison with
+    torch.optim.SGD itself is in test_optim_gpu.py."""
     from distribuuuu_amd.ops.optim import HIPSGD
 
     _ext()
