@@ -7,6 +7,8 @@ at::Tensor relu_bwd(at::Tensor gy, at::Tensor y);
 at::Tensor add_relu_fwd(at::Tensor a, at::Tensor b);
 at::Tensor se_scale_fwd(at::Tensor x, at::Tensor s);
 at::Tensor dropout_fwd(at::Tensor x, double p, int64_t seed);
+at::Tensor dropout_fwd_dev(at::Tensor x, double p, int64_t salt,
+                           at::Tensor step_dev);
 std::vector<at::Tensor> se_scale_bwd(at::Tensor gy, at::Tensor x,
                                      at::Tensor s);
 // bn.hip
@@ -140,6 +142,8 @@ bool is_deterministic();
 // sgd.hip
 void sgd_step(at::Tensor table, double lr, double momentum,
               double dampening, double weight_decay, bool nesterov);
+void sgd_step_dev(at::Tensor table, at::Tensor lr_dev, double momentum,
+                  double dampening, double weight_decay, bool nesterov);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("relu_fwd", &relu_fwd);
@@ -147,6 +151,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("add_relu_fwd", &add_relu_fwd);
   m.def("se_scale_fwd", &se_scale_fwd);
   m.def("dropout_fwd", &dropout_fwd);
+  m.def("dropout_fwd_dev", &dropout_fwd_dev);
   m.def("se_scale_bwd", &se_scale_bwd);
   m.def("bn_sums", &bn_sums);
   m.def("bn_reduce_partials", &bn_reduce_partials);
@@ -182,6 +187,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_bwd", &ce_bwd);
   m.def("topk_acc", &topk_acc);
   m.def("sgd_step", &sgd_step);
+  m.def("sgd_step_dev", &sgd_step_dev);
   m.def("conv2d_fwd", &conv2d_fwd);
   m.def("conv2d_fwd_v1", &conv2d_fwd_v1);
   m.def("conv2d_fwd_bn", &conv2d_fwd_bn);

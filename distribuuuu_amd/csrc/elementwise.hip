@@ -310,15 +310,36 @@ DEV_INLINE float u01_from(uint64_t z) {
   return (float)(z >> 40) * (1.0f / 16777216.0f);  // 24-bit mantissa
 }
 
-template <typename T, bool BWD>
-__global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y,
-                               int64_t total, float p, float inv_keep,
-                               uint64_t seed) {
+// Shared by both kernels below, which differ only in where the seed comes from.
+template <typename T>
+DEV_INLINE void dropout_body(const T* __restrict__ x, T* __restrict__ y,
+                             int64_t total, float p, float inv_keep,
+                             uint64_t seed) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (int64_t)gridDim.x * blockDim.x) {
     const bool keep = u01_from(seed ^ (uint64_t)i) >= p;
     y[i] = keep ? from_f32<T>(to_f32(x[i]) * inv_keep) : from_f32<T>(0.f);
   }
+}
+
+template <typename T, bool BWD>
+__global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y,
+                               int64_t total, float p, float inv_keep,
+                               uint64_t seed) {
+  dropout_body<T>(x, y, total, p, inv_keep, seed);
+}
+
+// Seed = salt + step * golden ratio (wrapping uint64), with `step` loaded
+// from device memory: a captured hipGraph draws a new mask on every replay
+// once the counter is advanced between replays.
+template <typename T>
+__global__ void dropout_kernel_dev(const T* __restrict__ x, T* __restrict__ y,
+                                   int64_t total, float p, float inv_keep,
+                                   uint64_t salt,
+                                   const long long* __restrict__ step_dev) {
+  const uint64_t seed =
+      salt + (uint64_t)(*step_dev) * 0x9e3779b97f4a7c15ULL;
+  dropout_body<T>(x, y, total, p, inv_keep, seed);
 }
 
 }  // namespace
@@ -333,6 +354,25 @@ at::Tensor dropout_fwd(at::Tensor x, double p, int64_t seed) {
                        (const scalar_t*)x.data_ptr(),
                        (scalar_t*)y.data_ptr(), total, (float)p,
                        1.f / (1.f - (float)p), (uint64_t)seed);
+  });
+  return y;
+}
+
+at::Tensor dropout_fwd_dev(at::Tensor x, double p, int64_t salt,
+                           at::Tensor step_dev) {
+  CHECK_GPU(x);
+  CHECK_GPU(step_dev);
+  TORCH_CHECK(step_dev.scalar_type() == at::kLong && step_dev.numel() == 1,
+              "dropout_fwd_dev: step must be an int64 tensor of one element");
+  auto y = at::empty_like(x);
+  const int64_t total = x.numel();
+  DISPATCH_FLOAT_AND_BF16(x.scalar_type(), "dropout_fwd_dev", [&] {
+    hipLaunchKernelGGL((dropout_kernel_dev<scalar_t>),
+                       dim3(grid_1d(total, 256)), dim3(256), 0, cur_stream(),
+                       (const scalar_t*)x.data_ptr(),
+                       (scalar_t*)y.data_ptr(), total, (float)p,
+                       1.f / (1.f - (float)p), (uint64_t)salt,
+                       (const long long*)step_dev.data_ptr());
   });
   return y;
 }

@@ -14,8 +14,11 @@
 
 namespace {
 
-__global__ void sgd_kernel(const long long* __restrict__ recs, float lr,
-                           float mu, float damp, float wd, int nesterov) {
+// Per-chunk update body shared by both kernels below: the only difference
+// between them is where `lr` comes from, so they compile to the same
+// arithmetic and give bit-identical results for the same rate.
+DEV_INLINE void sgd_chunk(const long long* __restrict__ recs, float lr,
+                          float mu, float damp, float wd, int nesterov) {
   const long long* rec = recs + (int64_t)blockIdx.x * 6;
   const void* grad = (const void*)rec[0];
   void* param = (void*)rec[1];
@@ -44,6 +47,21 @@ __global__ void sgd_kernel(const long long* __restrict__ recs, float lr,
   }
 }
 
+__global__ void sgd_kernel(const long long* __restrict__ recs, float lr,
+                           float mu, float damp, float wd, int nesterov) {
+  sgd_chunk(recs, lr, mu, damp, wd, nesterov);
+}
+
+// Learning rate read from device memory (one load per thread, before the
+// element loop): a captured hipGraph follows the schedule instead of freezing
+// the rate it was captured with.
+__global__ void sgd_kernel_dev(const long long* __restrict__ recs,
+                               const float* __restrict__ lr_dev, float mu,
+                               float damp, float wd, int nesterov) {
+  const float lr = *lr_dev;
+  sgd_chunk(recs, lr, mu, damp, wd, nesterov);
+}
+
 }  // namespace
 
 void sgd_step(at::Tensor table, double lr, double momentum, double dampening,
@@ -56,4 +74,19 @@ void sgd_step(at::Tensor table, double lr, double momentum, double dampening,
                      (const long long*)table.data_ptr(), (float)lr,
                      (float)momentum, (float)dampening, (float)weight_decay,
                      nesterov ? 1 : 0);
+}
+
+void sgd_step_dev(at::Tensor table, at::Tensor lr_dev, double momentum,
+                  double dampening, double weight_decay, bool nesterov) {
+  CHECK_GPU(table);
+  CHECK_GPU(lr_dev);
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.size(1) == 6,
+              "sgd table must be int64 [n, 6]");
+  TORCH_CHECK(lr_dev.scalar_type() == at::kFloat && lr_dev.numel() == 1,
+              "sgd_step_dev: lr must be a float32 tensor of one element");
+  const int n = table.size(0);
+  hipLaunchKernelGGL(sgd_kernel_dev, dim3(n), dim3(256), 0, cur_stream(),
+                     (const long long*)table.data_ptr(),
+                     (const float*)lr_dev.data_ptr(), (float)momentum,
+                     (float)dampening, (float)weight_decay, nesterov ? 1 : 0);
 }

@@ -742,7 +742,13 @@ class _HIPLinear(torch.autograd.Function):
         gy = gy.contiguous()
         e = ext()
         gx = e.gemm_nt(gy, w.t().contiguous())
-        gw = e.gemm_nt(gy.t().contiguous(), x.t().contiguous())
+        gyt, xt = gy.t(), x.t()
+        pad = _pad8(gy.shape[0]) - gy.shape[0]
+        if pad:
+            # the GEMM reduces over the batch and needs it 8-aligned: zero
+            # rows add nothing (a loader's last, shorter batch)
+            gyt, xt = F.pad(gyt, (0, pad)), F.pad(xt, (0, pad))
+        gw = e.gemm_nt(gyt.contiguous(), xt.contiguous())
         gb = gy.sum(0) if ctx.has_bias else None
         return gx, gw, gb
 
@@ -789,8 +795,8 @@ def cross_entropy(logits, target):
 class _HIPDropout(torch.autograd.Function):
     """Mask = hash(seed, element index) in the channels_last layout, so
     backward regenerates it bit-exactly. The seed is drawn host-side per
-    call; under hipGraph capture it would freeze across replays (all
-    baseline configs train with p = 0)."""
+    call; under hipGraph capture it would freeze across replays, which is
+    what the step counter below is for."""
 
     @staticmethod
     def forward(ctx, x, p, seed):
@@ -803,11 +809,59 @@ class _HIPDropout(torch.autograd.Function):
         return ext().dropout_fwd(_cl(gy), ctx.p, ctx.seed), None, None
 
 
+class _HIPDropoutDev(torch.autograd.Function):
+    """Same mask hash with the seed formed in the kernel from a host-drawn
+    salt (fixed per call site once captured) and a device step counter. The
+    counter only advances between steps, so backward regenerates the
+    forward's mask."""
+
+    @staticmethod
+    def forward(ctx, x, p, salt, step):
+        ctx.p = p
+        ctx.salt = salt
+        ctx.step = step
+        return ext().dropout_fwd_dev(_cl(x), p, salt, step)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return (ext().dropout_fwd_dev(_cl(gy), ctx.p, ctx.salt, ctx.step),
+                None, None, None)
+
+
+# int64[1] device tensor while a captured train step is being recorded
+# (graph_step.GraphedTrainStep), else None
+_STEP_COUNTER = None
+_STEP_COUNTER_USES = 0
+
+
+def install_step_counter(counter):
+    """Key every GPU dropout mask drawn from now on by `counter` (an int64
+    device tensor of one element) instead of a host-drawn seed alone."""
+    global _STEP_COUNTER, _STEP_COUNTER_USES
+    if counter.dtype != torch.int64 or counter.numel() != 1:
+        raise ValueError("step counter must be an int64 tensor of one element")
+    _STEP_COUNTER = counter
+    _STEP_COUNTER_USES = 0
+
+
+def remove_step_counter():
+    """Back to host-drawn seeds; returns how many dropout calls used the
+    counter while it was installed."""
+    global _STEP_COUNTER
+    _STEP_COUNTER = None
+    return _STEP_COUNTER_USES
+
+
 def dropout(x, p, training):
+    global _STEP_COUNTER_USES
     if p == 0.0 or not training:
         return x
     if use_hip(x, "dropout_fwd"):
         import random as _random
 
-        return _HIPDropout.apply(x, p, _random.getrandbits(62))
+        seed = _random.getrandbits(62)
+        if _STEP_COUNTER is not None and use_hip(x, "dropout_fwd_dev"):
+            _STEP_COUNTER_USES += 1
+            return _HIPDropoutDev.apply(x, p, seed, _STEP_COUNTER)
+        return _HIPDropout.apply(x, p, seed)
     return F.dropout(x, p, training)

@@ -17,6 +17,13 @@ stride-aware tensor math of the fallback instead (with a one-time warning).
 Both paths follow torch.optim.SGD semantics (reference utils.py:187-196:
 momentum + nesterov + weight decay + dampening), including the first step of
 a parameter, which seeds the momentum buffer with the un-dampened gradient.
+
+For a hipGraph-captured step (graph_step.GraphedTrainStep) two things are
+opt-in or automatic: device-rate mode reads the learning rate from a float32
+device tensor per group (``enable_device_lr`` / ``sync_device_lr``), so a
+replayed graph follows the schedule; and a ``step()`` issued while the stream
+is capturing builds its chunk table into a pinned/device pair of its own,
+which eager steps and ``state_dict()`` never touch.
 """
 
 import warnings
@@ -28,6 +35,11 @@ from .dispatch import hip_op_available, ext
 
 _CHUNK = 16384
 _FLAG_FRESH = 4  # sgd.hip: momentum uninitialised (first step)
+
+
+def _capturing():
+    return (torch.cuda.is_available()
+            and torch.cuda.is_current_stream_capturing())
 
 
 def _layout(t):
@@ -51,6 +63,98 @@ class HIPSGD(SGD):
 
     _warned_layout = False
 
+    # class-level defaults: instances unpickled from older checkpoints (and
+    # __init__ itself, which torch defines) need no extra set-up
+    generation = 0       # bumped whenever state tensors are replaced
+    _lr_dev = None       # device-rate mode: one float32[1] tensor per group
+    _lr_last = None      # ... and the host value last uploaded into each
+    _private = None      # capture-private (pinned, device) table per group
+
+    # -- device-rate mode --------------------------------------------------
+    def enable_device_lr(self):
+        """The fused kernel reads each group's rate from a float32[1] tensor
+        on the group's device instead of a launch argument. Call
+        sync_device_lr() after changing group["lr"]."""
+        self._lr_dev, self._lr_last = [], []
+        for group in self.param_groups:
+            lr = float(group["lr"])
+            self._lr_dev.append(torch.full(
+                (1,), lr, dtype=torch.float32,
+                device=group["params"][0].device))
+            self._lr_last.append(lr)
+
+    def disable_device_lr(self):
+        self._lr_dev = self._lr_last = None
+
+    def device_lr_blocker(self):
+        """Why the fused step cannot run in device-rate mode (a string), or
+        None. Parameters on the stride-aware path are known once a step has
+        built the chunk table, so ask again after the first step."""
+        if not hip_op_available("sgd_step_dev"):
+            return "fused sgd_step_dev kernel unavailable"
+        for group in self.param_groups:
+            if not group["params"][0].is_cuda:
+                return "parameters are not on the GPU"
+            cache = group.get("_hip_table")
+            if cache is not None and cache[2]:
+                return (f"{len(cache[2])} parameter(s) take the stride-aware "
+                        "update outside the fused kernel")
+        return None
+
+    def sync_device_lr(self):
+        """Upload every group["lr"] that differs from the value last
+        uploaded; returns how many were. A host float compare per group
+        otherwise."""
+        if self._lr_dev is None:
+            return 0
+        n = 0
+        for i, group in enumerate(self.param_groups):
+            lr = float(group["lr"])
+            if lr != self._lr_last[i]:
+                self._lr_dev[i].fill_(lr)
+                self._lr_last[i] = lr
+                n += 1
+        return n
+
+    # -- capture-private chunk table ---------------------------------------
+    def reserve_capture_tables(self):
+        """Allocate the capture-private table pair of every GPU group ahead
+        of the capture (pinned host memory is best not allocated while a
+        stream is capturing). Sized like the eager table when a step has
+        built one, else for every trainable parameter."""
+        if self._private is None:
+            self._private = {}
+        for gi, group in enumerate(self.param_groups):
+            if not group["params"][0].is_cuda:
+                continue
+            pin = group.get("_hip_table_pin")
+            if pin is not None:
+                nrec = pin.numel() // 6
+            else:
+                nrec = sum(-(-p.numel() // _CHUNK) for p in group["params"]
+                           if p.requires_grad)
+            self._private_pair(gi, group, nrec)
+
+    def _private_pair(self, gi, group, nrec):
+        pair = self._private.get(gi)
+        if pair is None or pair[0].shape[0] != nrec:
+            if pair is not None and pair[2]:
+                raise RuntimeError(
+                    "HIPSGD: a captured graph owns this group's private "
+                    "chunk table and the new step needs another size; "
+                    "call release_capture_tables() after dropping the graph")
+            pin = torch.empty((nrec, 6), dtype=torch.int64, pin_memory=True)
+            dev = torch.empty((nrec, 6), dtype=torch.int64,
+                              device=group["params"][0].device)
+            pair = self._private[gi] = [pin, dev, False]
+        return pair
+
+    def release_capture_tables(self):
+        """Drop the capture-private tables. Only after the graph that was
+        captured with them is gone: it replays the pinned-to-device copy and
+        holds raw pointers to both."""
+        self._private = None
+
     def _init_state(self, p):
         """Create momentum (+ master) state; True when it was just created,
         i.e. this is the parameter's first step."""
@@ -65,7 +169,11 @@ class HIPSGD(SGD):
 
     def _build_table(self, group):
         """Returns (device table, params to update with stride-aware math,
-        whether any record carries the first-step flag)."""
+        whether any record carries the first-step flag). While the stream is
+        capturing the table goes into the group's capture-private pair and
+        the eager pair is left alone."""
+        capturing = _capturing()
+        gi = next(i for i, g in enumerate(self.param_groups) if g is group)
         recs = []
         strided = []
         any_fresh = False
@@ -115,6 +223,23 @@ class HIPSGD(SGD):
         # zero_grad(set_to_none=True)) only do host writes + one capturable
         # async H2D copy into the existing device tensor.
         cpu = torch.tensor(recs, dtype=torch.int64).reshape(-1, 6)
+        if capturing:
+            if any_fresh:
+                raise RuntimeError(
+                    "HIPSGD: a parameter's first step cannot be captured "
+                    "(its first-step flag would replay); run one eager step "
+                    "before capturing")
+            if self._private is None:
+                self._private = {}
+            pair = self._private_pair(gi, group, cpu.shape[0])
+            if pair[2]:
+                raise RuntimeError(
+                    "HIPSGD: one captured step() per graph; call "
+                    "release_capture_tables() after dropping the graph")
+            pair[2] = True  # a graph now replays the copy below
+            pair[0].copy_(cpu)
+            pair[1].copy_(pair[0], non_blocking=True)
+            return pair[1], strided, any_fresh
         pin = group.get("_hip_table_pin")
         table = group.get("_hip_table_dev")
         if pin is None or pin.numel() != cpu.numel():
@@ -122,6 +247,13 @@ class HIPSGD(SGD):
             table = pin.to(device, non_blocking=True)
             group["_hip_table_pin"] = pin
             group["_hip_table_dev"] = table
+            # a later captured step needs a pair of this size and must not
+            # allocate pinned memory while capturing: set it aside now
+            # (allocated, never written here)
+            if not (self._private or {}).get(gi, (None, None, False))[2]:
+                if self._private is None:
+                    self._private = {}
+                self._private_pair(gi, group, cpu.shape[0])
         else:
             pin.copy_(cpu)
             table.copy_(pin, non_blocking=True)
@@ -137,10 +269,22 @@ class HIPSGD(SGD):
         if not hip_op_available("sgd_step"):
             return self._fallback_step(loss)
 
-        for group in self.param_groups:
+        capturing = _capturing()
+        if not capturing:
+            self.sync_device_lr()
+        for gi, group in enumerate(self.param_groups):
             if not group["params"][0].is_cuda:
                 # host-resident model on a GPU machine: tensor ops
                 self._fallback_group(group)
+                continue
+            if capturing:
+                # never read or written by eager steps, and the other way round
+                table, strided, _ = self._build_table(group)
+                if strided:
+                    raise RuntimeError(
+                        "HIPSGD: parameters on the stride-aware path cannot "
+                        "be captured")
+                self._launch(gi, group, table)
                 continue
             cache = group.get("_hip_table")
             # the grad's strides are part of the key: the kernel's linear
@@ -160,12 +304,7 @@ class HIPSGD(SGD):
                                        strided)
             else:
                 table, strided = cache[0], cache[2]
-            if table.numel():
-                # torch ignores dampening when there is no momentum
-                damp = group["dampening"] if group["momentum"] != 0 else 0.0
-                ext().sgd_step(table, group["lr"], group["momentum"],
-                               damp, group["weight_decay"],
-                               group["nesterov"])
+            self._launch(gi, group, table)
             if strided:
                 for p, fresh in strided:
                     self._update_param(p, group, fresh)
@@ -174,7 +313,21 @@ class HIPSGD(SGD):
                                        [(p, False) for p, _ in strided])
         return loss
 
+    def _launch(self, gi, group, table):
+        if not table.numel():
+            return
+        # torch ignores dampening when there is no momentum
+        damp = group["dampening"] if group["momentum"] != 0 else 0.0
+        if self._lr_dev is not None:
+            ext().sgd_step_dev(table, self._lr_dev[gi], group["momentum"],
+                               damp, group["weight_decay"], group["nesterov"])
+        else:
+            ext().sgd_step(table, group["lr"], group["momentum"], damp,
+                           group["weight_decay"], group["nesterov"])
+
     def _drop_table_cache(self):
+        # the capture-private pair stays: a graph may still replay it, and
+        # whoever holds that graph calls release_capture_tables()
         for group in self.param_groups:
             group.pop("_hip_table", None)
             group.pop("_hip_table_pin", None)
@@ -190,6 +343,9 @@ class HIPSGD(SGD):
         # embeds their raw pointers, so it must be rebuilt on the next step
         super().load_state_dict(state_dict)
         self._drop_table_cache()
+        # a captured graph still points at the replaced tensors: its owner
+        # compares this counter and captures again
+        self.generation += 1
         # the table kernel requires fp32 momentum/master on the param's device
         # (their strides are checked, and fixed, when the table is built).
         # torch casts loaded state to the PARAMETER's dtype, which would round

@@ -20,6 +20,7 @@ import torch
 from . import models
 from .config import cfg
 from .data import construct_train_loader, construct_val_loader
+from .graph_step import GraphedTrainStep
 from .logger import logger, setup_logger
 from .ops import functional as DF
 from .parallel import DistributedDataParallel, convert_sync_batchnorm
@@ -58,9 +59,36 @@ def build_network(device):
     return net
 
 
-def train_epoch(train_loader, net, criterion, optimizer, epoch, device, dtype):
-    """One epoch of the hot loop (reference trainer.py:14-64)."""
+def _own_runner(net, criterion, optimizer, topk, device, dtype):
+    """The runner of a train_epoch call that was given none: built at the
+    first such call and kept on the optimizer, so later epochs replay the
+    graph that the first one captured. One runner per optimizer: a second
+    one would find the capture-private chunk table owned by the first, so a
+    call with another network or loss trains eagerly and says so."""
+    runner = getattr(optimizer, "_graph_step", None)
+    if runner is None:
+        runner = optimizer._graph_step = GraphedTrainStep(
+            net, criterion, optimizer, topk, device=device, dtype=dtype)
+    elif runner.net is not net or runner.criterion is not criterion:
+        if utils.get_rank() == 0:
+            logger.info("TRAIN.COMPILE_GRAPH: this optimizer's runner was "
+                        "built for another network or loss; training "
+                        "eagerly")
+        return None
+    return runner
+
+
+def train_epoch(train_loader, net, criterion, optimizer, epoch, device, dtype,
+                graph_step=None):
+    """One epoch of the hot loop (reference trainer.py:14-64). With a
+    `graph_step` runner (graph_step.GraphedTrainStep; when
+    cfg.TRAIN.COMPILE_GRAPH is set and none is passed, the optimizer's own,
+    see _own_runner) the step itself is a hipGraph replay; meters, readout
+    and LR cadence are the same."""
     topk = cfg.TRAIN.TOPK
+    if graph_step is None and cfg.TRAIN.COMPILE_GRAPH:
+        graph_step = _own_runner(net, criterion, optimizer, topk, device,
+                                 dtype)
     (batch_time, data_time, losses, top1, topk_m, ips,
      progress) = utils.construct_meters(
         len(train_loader), f"Epoch[{epoch + 1}/{cfg.OPTIM.MAX_EPOCH}]", topk,
@@ -79,13 +107,16 @@ def train_epoch(train_loader, net, criterion, optimizer, epoch, device, dtype):
     end = time.time()
     for idx, (inputs, targets) in enumerate(train_loader):
         data_time.update(time.time() - end)
-        inputs, targets = _prepare_batch(inputs, targets, device, dtype)
-        outputs = net(inputs)
-        loss = criterion(outputs.float(), targets)
-        optimizer.zero_grad(set_to_none=zero_none)
-        loss.backward()
-        optimizer.step()
-        acc1, acck = utils.accuracy(outputs, targets, topk=(1, topk))
+        if graph_step is not None:
+            loss, acc1, acck = graph_step(inputs, targets)
+        else:
+            inputs, targets = _prepare_batch(inputs, targets, device, dtype)
+            outputs = net(inputs)
+            loss = criterion(outputs.float(), targets)
+            optimizer.zero_grad(set_to_none=zero_none)
+            loss.backward()
+            optimizer.step()
+            acc1, acck = utils.accuracy(outputs, targets, topk=(1, topk))
         if (idx % cfg.TRAIN.PRINT_FREQ == 0) or (idx + 1 == len(train_loader)):
             metrics = [loss.detach(), acc1[0], acck[0]]
             utils.scaled_all_reduce(metrics)
@@ -165,8 +196,16 @@ def train_model():
         if rank == 0:
             logger.info(f"Loaded initial weights from {cfg.MODEL.WEIGHTS}")
 
+    # after resume/weight loading: the runner captures these tensors
+    graph_step = None
+    if cfg.TRAIN.COMPILE_GRAPH:
+        graph_step = GraphedTrainStep(net, criterion, optimizer,
+                                      cfg.TRAIN.TOPK, device=device,
+                                      dtype=dtype)
+
     for epoch in range(start_epoch, cfg.OPTIM.MAX_EPOCH):
-        train_epoch(train_loader, net, criterion, optimizer, epoch, device, dtype)
+        train_epoch(train_loader, net, criterion, optimizer, epoch, device,
+                    dtype, graph_step=graph_step)
         acc1, acck = validate(val_loader, net, criterion, device, dtype)
         best = acc1 > best_acc1
         best_acc1 = max(acc1, best_acc1)
