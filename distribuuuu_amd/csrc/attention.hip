@@ -176,7 +176,9 @@ __global__ __launch_bounds__(256) void mhsa_fwd_kernel(MhsaParams p) {
       const int kpos = nt * 16 + il;
       const __hip_bfloat16 pv =
           from_f32<__hip_bfloat16>(sacc[nt][rr] * rsum[rr]);
-      prow[kpos] = pv;
+      // 16*LT can exceed lpad = roundup32(L): unguarded, the pad columns of
+      // row r land in (and zero) the head of row r+1, already written
+      if (kpos < p.lpad) prow[kpos] = pv;
       if (gp && kpos < p.L) gp[kpos] = pv;
     }
     // lpad tail beyond LT*16 (LT*16 >= ltiles16*16 covers it; pad cols in
@@ -347,7 +349,7 @@ __global__ __launch_bounds__(256) void mhsa_bwd_q_kernel(MhsaBwdQParams p) {
       const float dsv =
           ok ? to_f32(prow[kpos]) * (dacc[nt][rr] - dot[rr]) : 0.f;
       const __hip_bfloat16 dsb = from_f32<__hip_bfloat16>(dsv);
-      dsrow[kpos] = dsb;
+      if (kpos < p.lpad) dsrow[kpos] = dsb;  // as in the forward P store
       if (gds && kpos < p.L) gds[kpos] = dsb;
     }
     for (int j = LT * 16 + il; j < p.lpad; j += 16)
@@ -717,10 +719,27 @@ std::vector<at::Tensor> mhsa_bwd(at::Tensor dO, at::Tensor P, at::Tensor q,
                                  int64_t opix, double scale,
                                  at::Tensor dqk_out, at::Tensor dv_out) {
   CHECK_GPU(dO);
+  TORCH_CHECK(P.scalar_type() == at::kBFloat16 &&
+                  dO.scalar_type() == at::kBFloat16 &&
+                  v.scalar_type() == at::kBFloat16,
+              "mhsa_bwd: P, dO and v must be bf16");
+  TORCH_CHECK(P.dim() == 3 && P.size(1) == P.size(2) && P.is_contiguous(),
+              "mhsa_bwd: P must be contiguous [B, L, L]");
+  TORCH_CHECK(rel_w.dim() == 2 && rel_h.dim() == 2,
+              "mhsa_bwd: rel_w / rel_h must be 2-D");
   const int B = P.size(0), L = P.size(1);
   const int D = rel_w.size(1);
   const int MW = 2 * W - 1, MH = 2 * H - 1;
-  TORCH_CHECK(MW <= 32 && MH <= 32, "mhsa_bwd: rel table > 32");
+  TORCH_CHECK(H >= 1 && W >= 1 && MW <= 32 && MH <= 32,
+              "mhsa_bwd: rel table > 32");
+  TORCH_CHECK(D % 32 == 0 && D >= 32 && D <= 128,
+              "mhsa_bwd: D must be <=128, %32==0, got ", D);
+  TORCH_CHECK(L == H * W, "mhsa_bwd: L = ", L, " != H*W = ", H * W);
+  // the dq fold reads rel_w[m * D + d] for m < 2W-1 (rel_h: m < 2H-1)
+  TORCH_CHECK(rel_w.size(0) == MW && rel_w.size(1) == D,
+              "mhsa_bwd: rel_w must be [2W-1, D]");
+  TORCH_CHECK(rel_h.size(0) == MH && rel_h.size(1) == D,
+              "mhsa_bwd: rel_h must be [2H-1, D]");
   auto ds = at::empty_like(P);
   auto fopts = P.options().dtype(at::kFloat);
   auto drw = at::empty({(int64_t)B * L, MW}, fopts);
@@ -826,10 +845,33 @@ at::Tensor mhsa_fwd(at::Tensor q, at::Tensor k, at::Tensor vt, at::Tensor rw,
                     c10::optional<at::Tensor> pout, int64_t heads,
                     int64_t qpix, int64_t kpix, double scale) {
   CHECK_GPU(q);
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16, "mhsa: bf16 only");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 &&
+                  k.scalar_type() == at::kBFloat16 &&
+                  vt.scalar_type() == at::kBFloat16,
+              "mhsa: q, k and vt must be bf16");
+  TORCH_CHECK(vt.dim() == 3 && vt.is_contiguous(), "mhsa: vt must be [B, D, L]");
   const int B = vt.size(0), D = vt.size(1), L = vt.size(2);
   TORCH_CHECK(D % 32 == 0 && D <= 128, "mhsa: D must be <=128, %32==0");
+  TORCH_CHECK(H >= 1 && H <= 16 && W >= 1 && W <= 16,
+              "mhsa: H and W must be in [1, 16], got ", H, "x", W);
   TORCH_CHECK(L == H * W, "L != H*W");
+  TORCH_CHECK(heads >= 1 && B % heads == 0,
+              "mhsa: B = ", B, " is not a multiple of heads = ", heads);
+  // the kernel strides the tables by 2W-1 / 2H-1 and pout by L
+  TORCH_CHECK(rw.scalar_type() == at::kFloat && rw.is_contiguous() &&
+                  rw.dim() == 3 && rw.size(0) == B && rw.size(1) == L &&
+                  rw.size(2) == 2 * W - 1,
+              "mhsa: rw must be contiguous fp32 [B, L, 2W-1]");
+  TORCH_CHECK(rh.scalar_type() == at::kFloat && rh.is_contiguous() &&
+                  rh.dim() == 3 && rh.size(0) == B && rh.size(1) == L &&
+                  rh.size(2) == 2 * H - 1,
+              "mhsa: rh must be contiguous fp32 [B, L, 2H-1]");
+  if (pout.has_value())
+    TORCH_CHECK(pout->scalar_type() == at::kBFloat16 &&
+                    pout->is_contiguous() && pout->dim() == 3 &&
+                    pout->size(0) == B && pout->size(1) == L &&
+                    pout->size(2) == L,
+                "mhsa: pout must be contiguous bf16 [B, L, L]");
   const int N = B / (int)heads;
   at::Tensor o;
   int64_t opix;

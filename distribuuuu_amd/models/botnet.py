@@ -18,7 +18,8 @@ import torch.nn as nn
 
 from ..ops import AdaptiveAvgPool2d, AvgPool2d, BatchNorm2d, Conv2d, Linear
 from ..ops import functional as DF
-from ..ops.attention import mhsa_relpos, mhsa_relpos_nhwc
+from ..ops.attention import (check_rel_tables, hip_mhsa_supported,
+                             mhsa_relpos, mhsa_relpos_nhwc)
 from .resnet import resnet50
 
 
@@ -55,9 +56,13 @@ class MHSA(nn.Module):
         n, _, hh, ww = x.shape
         qk = self.to_qk(x)
         v = self.to_v(x)
+        if self.rel_pos_emb:
+            check_rel_tables(self.rel_h, self.rel_w, hh, ww)
+        # outside the fused kernels' range (L <= 256, H, W <= 16, head dim a
+        # multiple of 32 up to 128) mhsa_relpos below warns once and composes
         if (self.rel_pos_emb and self.dim_qk == self.dim_v
                 and qk.is_cuda and qk.dtype == torch.bfloat16
-                and self.dim_qk % 32 == 0 and self.dim_qk <= 128):
+                and hip_mhsa_supported(hh, ww, self.dim_qk)):
             from ..ops.dispatch import use_hip
             if use_hip(qk, "mhsa_fwd"):
                 # NHWC in-place path: the qkv convs' channels_last outputs

@@ -130,14 +130,35 @@ class _HIPMHSARelPos(torch.autograd.Function):
                 grw.to(rel_w.dtype), None, None)
 
 
+def check_rel_tables(rel_h, rel_w, h, w):
+    """The kernels (and the pad-shift composition) index the tables with the
+    activation's own H and W; a map of another size than the tables were
+    built for would read them at the wrong stride."""
+    if rel_h.shape[0] != 2 * h - 1 or rel_w.shape[0] != 2 * w - 1:
+        raise ValueError(
+            f"MHSA: activation is {h}x{w} but the relative-position tables "
+            f"are sized for {(rel_h.shape[0] + 1) // 2}x"
+            f"{(rel_w.shape[0] + 1) // 2} (rel_h {tuple(rel_h.shape)}, "
+            f"rel_w {tuple(rel_w.shape)})")
+
+
+def hip_mhsa_supported(h, w, d):
+    """Range of the fused kernels: register logits hold at most 16 tiles of
+    16 keys (L <= 256), the rel tables at most 31 columns (H, W <= 16), the
+    head dim 1..4 MFMA K-steps of 32."""
+    return (1 <= h <= 16 and 1 <= w <= 16 and h * w <= 256
+            and d % 32 == 0 and 32 <= d <= 128)
+
+
 def mhsa_relpos(q, k, v, rel_h, rel_w, h, w):
     """q (pre-scaled), k, v: [N, heads, L, d]; returns [N, heads, L, d_v]."""
+    check_rel_tables(rel_h, rel_w, h, w)
     if (use_hip(q, "mhsa_fwd") and q.dtype == torch.bfloat16
-            and q.shape[-1] % 32 == 0 and q.shape[-1] <= 128):
+            and hip_mhsa_supported(h, w, q.shape[-1])):
         return _HIPMHSARelPos.apply(q, k, v, rel_h, rel_w, h, w)
     if q.is_cuda:
         fallback_warn("mhsa_relpos",
-                      f"dtype {q.dtype} head_dim {q.shape[-1]}")
+                      f"dtype {q.dtype} head_dim {q.shape[-1]} map {h}x{w}")
     return _torch_mhsa(q, k, v, rel_h, rel_w, h, w)
 
 
@@ -168,6 +189,8 @@ class _HIPMHSARelPosNHWC(torch.autograd.Function):
                                scale)
         rh = e.mhsa_rel_tables(qkc, rel_h.contiguous(), rows, heads, l, qpix,
                                scale)
+        rw = rw.reshape(n * heads, l, -1)
+        rh = rh.reshape(n * heads, l, -1)
         need_grad = any(t.requires_grad for t in (qk, v, rel_h, rel_w))
         pout = (torch.empty(n * heads, l, l, dtype=qk.dtype, device=qk.device)
                 if need_grad else None)
