@@ -215,6 +215,9 @@ _C.OPTIM.WARMUP_FACTOR = 0.1
 _C.OPTIM.WARMUP_EPOCHS = 5
 _C.OPTIM.WEIGHT_DECAY = 5e-5
 _C.OPTIM.FUSED_SGD = True            # fused multi-tensor HIP SGD step on GPU
+_C.OPTIM.OPTIMIZER = "sgd"           # "sgd" | "lars" (layer-wise adaptive rate)
+_C.OPTIM.LARS_TRUST_COEF = 0.001     # LARS trust coefficient
+_C.OPTIM.LARS_EPS = 1e-8             # added to the LARS ratio's denominator
 
 _C.OUT_DIR = "./exp"
 _C.CFG_DEST = "config.yaml"

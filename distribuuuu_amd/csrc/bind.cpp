@@ -144,6 +144,15 @@ void sgd_step(at::Tensor table, double lr, double momentum,
               double dampening, double weight_decay, bool nesterov);
 void sgd_step_dev(at::Tensor table, at::Tensor lr_dev, double momentum,
                   double dampening, double weight_decay, bool nesterov);
+// lars.hip
+void lars_step(at::Tensor table, int64_t nchunks, at::Tensor part,
+               at::Tensor sqnorm, at::Tensor q, double lr, double momentum,
+               double dampening, double weight_decay, bool nesterov,
+               double trust_coef, double eps);
+void lars_step_dev(at::Tensor table, int64_t nchunks, at::Tensor part,
+                   at::Tensor sqnorm, at::Tensor q, at::Tensor lr_dev,
+                   double momentum, double dampening, double weight_decay,
+                   bool nesterov, double trust_coef, double eps);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("relu_fwd", &relu_fwd);
@@ -188,6 +197,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topk_acc", &topk_acc);
   m.def("sgd_step", &sgd_step);
   m.def("sgd_step_dev", &sgd_step_dev);
+  m.def("lars_step", &lars_step);
+  m.def("lars_step_dev", &lars_step_dev);
   m.def("conv2d_fwd", &conv2d_fwd);
   m.def("conv2d_fwd_v1", &conv2d_fwd_v1);
   m.def("conv2d_fwd_bn", &conv2d_fwd_bn);

@@ -24,6 +24,9 @@ device tensor per group (``enable_device_lr`` / ``sync_device_lr``), so a
 replayed graph follows the schedule; and a ``step()`` issued while the stream
 is capturing builds its chunk table into a pinned/device pair of its own,
 which eager steps and ``state_dict()`` never touch.
+
+``HIPLARS`` (at the end of this file) is HIPSGD with a layer-wise trust ratio
+on the same table, cache and capture machinery (csrc/lars.hip).
 """
 
 import warnings
@@ -70,6 +73,11 @@ class HIPSGD(SGD):
     _lr_last = None      # ... and the host value last uploaded into each
     _private = None      # capture-private (pinned, device) table per group
 
+    # the extension ops behind step(); a subclass names its own pair
+    _step_op = "sgd_step"
+    _dev_op = "sgd_step_dev"
+    _fused = True        # False (HIPLARS(fused=False)): tensor ops throughout
+
     # -- device-rate mode --------------------------------------------------
     def enable_device_lr(self):
         """The fused kernel reads each group's rate from a float32[1] tensor
@@ -90,8 +98,8 @@ class HIPSGD(SGD):
         """Why the fused step cannot run in device-rate mode (a string), or
         None. Parameters on the stride-aware path are known once a step has
         built the chunk table, so ask again after the first step."""
-        if not hip_op_available("sgd_step_dev"):
-            return "fused sgd_step_dev kernel unavailable"
+        if not self._fused or not hip_op_available(self._dev_op):
+            return f"fused {self._dev_op} kernel unavailable"
         for group in self.param_groups:
             if not group["params"][0].is_cuda:
                 return "parameters are not on the GPU"
@@ -131,8 +139,8 @@ class HIPSGD(SGD):
             if pin is not None:
                 nrec = pin.numel() // 6
             else:
-                nrec = sum(-(-p.numel() // _CHUNK) for p in group["params"]
-                           if p.requires_grad)
+                nrec = sum(-(-p.numel() // _CHUNK) + self._rows_per_tensor
+                           for p in group["params"] if p.requires_grad)
             self._private_pair(gi, group, nrec)
 
     def _private_pair(self, gi, group, nrec):
@@ -179,7 +187,8 @@ class HIPSGD(SGD):
         any_fresh = False
         # momentum == 0 never reads the buffer's history: no first-step case
         seed_first = group["dampening"] != 0 and group["momentum"] != 0
-        for p in group["params"]:
+        tensors = []  # (first record, records, index in the group, param)
+        for pi, p in enumerate(group["params"]):
             if p.grad is None:
                 continue
             fresh = self._init_state(p)
@@ -203,12 +212,14 @@ class HIPSGD(SGD):
                         p, dtype=torch.float32).copy_(t)
             master = state.get("master", p)
             flags = (1 if p.dtype == torch.bfloat16 else 0) | (
-                2 if p.grad.dtype == torch.bfloat16 else 0)
+                2 if p.grad.dtype == torch.bfloat16 else 0) | (
+                self._extra_flags(pi))
             if fresh and seed_first:
                 flags |= _FLAG_FRESH
                 any_fresh = True
             n = p.numel()
             off = 0
+            first = len(recs)
             while off < n:
                 cnt = min(_CHUNK, n - off)
                 recs.append([p.grad.data_ptr(), p.data_ptr(),
@@ -216,6 +227,9 @@ class HIPSGD(SGD):
                              master.data_ptr(), off,
                              cnt | (flags << 32)])
                 off += _CHUNK
+            tensors.append((first, len(recs) - first, pi, p))
+        nchunks = len(recs)
+        recs += self._tensor_records(tensors)
         device = group["params"][0].device
         # pinned staging + async copy. The pinned buffer and device table are
         # allocated on the FIRST build (outside any hipGraph capture, during
@@ -239,6 +253,7 @@ class HIPSGD(SGD):
             pair[2] = True  # a graph now replays the copy below
             pair[0].copy_(cpu)
             pair[1].copy_(pair[0], non_blocking=True)
+            self._table_built(group, pair, nchunks)
             return pair[1], strided, any_fresh
         pin = group.get("_hip_table_pin")
         table = group.get("_hip_table_dev")
@@ -247,6 +262,9 @@ class HIPSGD(SGD):
             table = pin.to(device, non_blocking=True)
             group["_hip_table_pin"] = pin
             group["_hip_table_dev"] = table
+            ws = self._workspace(group, cpu.shape[0])
+            if ws is not None:
+                group["_hip_table_ws"] = ws
             # a later captured step needs a pair of this size and must not
             # allocate pinned memory while capturing: set it aside now
             # (allocated, never written here)
@@ -257,7 +275,29 @@ class HIPSGD(SGD):
         else:
             pin.copy_(cpu)
             table.copy_(pin, non_blocking=True)
+        self._table_built(group, None, nchunks)
         return table, strided, any_fresh
+
+    # -- hooks for an optimizer that rides on this table (HIPLARS) ----------
+    _rows_per_tensor = 0  # table rows a tensor adds beyond its chunks
+
+    def _extra_flags(self, pi):
+        """More bits for a chunk record's flags word; `pi` is the
+        parameter's index in its group."""
+        return 0
+
+    def _tensor_records(self, tensors):
+        """Rows appended after all chunk records."""
+        return []
+
+    def _workspace(self, group, nrec):
+        """Device scratch that lives and dies with a table pair of `nrec`
+        rows, or None."""
+        return None
+
+    def _table_built(self, group, pair, nchunks):
+        """A table was just written: `pair` is the capture-private pair, or
+        None for the group's eager one."""
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -266,7 +306,7 @@ class HIPSGD(SGD):
             with torch.enable_grad():
                 loss = closure()
 
-        if not hip_op_available("sgd_step"):
+        if not self._fused or not hip_op_available(self._step_op):
             return self._fallback_step(loss)
 
         capturing = _capturing()
@@ -306,8 +346,7 @@ class HIPSGD(SGD):
                 table, strided = cache[0], cache[2]
             self._launch(gi, group, table)
             if strided:
-                for p, fresh in strided:
-                    self._update_param(p, group, fresh)
+                self._update_strided(group, strided)
                 # first-step status is spent
                 group["_hip_table"] = (table, group["_hip_table"][1],
                                        [(p, False) for p, _ in strided])
@@ -332,6 +371,7 @@ class HIPSGD(SGD):
             group.pop("_hip_table", None)
             group.pop("_hip_table_pin", None)
             group.pop("_hip_table_dev", None)
+            group.pop("_hip_table_ws", None)
 
     def state_dict(self):
         # drop the pointer cache from serialized state
@@ -367,9 +407,14 @@ class HIPSGD(SGD):
                 state[k] = t.to(device=p.device, dtype=torch.float32,
                                 copy=True)
 
-    def _update_param(self, p, group, fresh):
+    def _update_strided(self, group, strided):
+        for p, fresh in strided:
+            self._update_param(p, group, fresh)
+
+    def _update_param(self, p, group, fresh, q=None):
         """Plain stride-aware SGD math for one parameter, with fp32 master
-        handling for bf16 params. `fresh`: first step of this parameter."""
+        handling for bf16 params. `fresh`: first step of this parameter.
+        `q`: a 0-dim tensor that scales g + wd*w (HIPLARS), or None."""
         lr = group["lr"]
         mu = group["momentum"]
         damp = group["dampening"]
@@ -380,6 +425,8 @@ class HIPSGD(SGD):
         w = state["master"] if low_prec else p.data
         if wd != 0:
             g = g.add(w, alpha=wd)
+        if q is not None:
+            g = g * q
         if mu != 0:
             buf = state["momentum_buffer"]
             if fresh:
@@ -405,3 +452,158 @@ class HIPSGD(SGD):
                 continue
             fresh = self._init_state(p)
             self._update_param(p, group, fresh)
+
+
+_SLOT_SHIFT = 8  # lars.hip: a chunk's tensor slot sits above the flag bits
+
+
+class HIPLARS(HIPSGD):
+    """HIPSGD with layer-wise adaptive rate scaling (You, Gitman, Ginsburg
+    2017). Per parameter tensor, with w the fp32 master and g the gradient:
+
+        W = sum(w*w), G = sum(g*g)
+        q = trust_coef * sqrt(W) / (sqrt(G) + wd*sqrt(W) + eps)
+            if p.ndim > 1 and W > 0 and G > 0, else 1
+
+    and the SGD-momentum update of HIPSGD runs on q * (g + wd*w). Tensors
+    with ndim <= 1 (BN weight and bias, biases) are never adapted.
+
+    The fused step is three launches on the group's chunk table (lars.hip):
+    per-chunk squared norms, a per-tensor combine that forms q, the update.
+    ``last_trust[gi]`` (float32 [len(params)]) and ``last_sqnorms[gi]``
+    (float32 [len(params), 2]: W, G) are device tensors holding what the
+    latest step of group ``gi`` computed; a parameter without a grad holds
+    q = 1 and zero norms.
+    """
+
+    _step_op = "lars_step"
+    _dev_op = "lars_step_dev"
+    _rows_per_tensor = 1
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0,
+                 weight_decay=0, nesterov=False, trust_coef=1e-3, eps=1e-8,
+                 fused=True):
+        if trust_coef < 0.0:
+            raise ValueError(f"Invalid trust_coef value: {trust_coef}")
+        if eps < 0.0:
+            raise ValueError(f"Invalid eps value: {eps}")
+        self._lars_defaults = dict(trust_coef=trust_coef, eps=eps)
+        super().__init__(params, lr=lr, momentum=momentum,
+                         dampening=dampening, weight_decay=weight_decay,
+                         nesterov=nesterov)
+        self.defaults.update(self._lars_defaults)
+        self._fused = bool(fused)
+        self.last_trust = {}
+        self.last_sqnorms = {}
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        for k, v in self._lars_defaults.items():
+            self.param_groups[-1].setdefault(k, v)
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        # groups saved by HIPSGD or torch.optim.SGD carry neither key
+        for group in self.param_groups:
+            for k, v in self._lars_defaults.items():
+                group.setdefault(k, v)
+
+    # -- table ---------------------------------------------------------------
+    def _extra_flags(self, pi):
+        return pi << _SLOT_SHIFT
+
+    def _tensor_records(self, tensors):
+        return [[first, n, pi, 1 if p.ndim > 1 else 0, 0, 0]
+                for first, n, pi, p in tensors]
+
+    def _workspace(self, group, nrec):
+        n = len(group["params"])
+        device = group["params"][0].device
+        return {"part": torch.empty(2 * nrec, dtype=torch.float32,
+                                    device=device),
+                "sqnorm": torch.zeros((n, 2), dtype=torch.float32,
+                                      device=device),
+                "q": torch.ones(n, dtype=torch.float32, device=device),
+                "nchunks": 0}
+
+    def _private_pair(self, gi, group, nrec):
+        pair = super()._private_pair(gi, group, nrec)
+        if len(pair) == 3:
+            pair.append(self._workspace(group, nrec))
+        return pair
+
+    def _table_built(self, group, pair, nchunks):
+        ws = pair[3] if pair is not None else group["_hip_table_ws"]
+        ws["nchunks"] = nchunks
+        # the kernels write the slots of tensors in the table; the others
+        # (no grad, or on the stride-aware path until its update) read so
+        ws["q"].fill_(1.0)
+        ws["sqnorm"].zero_()
+
+    def _launch(self, gi, group, table):
+        pair = (self._private or {}).get(gi)
+        private = pair is not None and table is pair[1]
+        ws = pair[3] if private else group["_hip_table_ws"]
+        if table.numel():
+            damp = group["dampening"] if group["momentum"] != 0 else 0.0
+            args = (group["momentum"], damp, group["weight_decay"],
+                    group["nesterov"], group["trust_coef"], group["eps"])
+            head = (table, ws["nchunks"], ws["part"], ws["sqnorm"], ws["q"])
+            if self._lr_dev is not None:
+                ext().lars_step_dev(*head, self._lr_dev[gi], *args)
+            else:
+                ext().lars_step(*head, group["lr"], *args)
+        if not private and pair is not None and pair[2]:
+            # a graph owns the private copy and its replays write there:
+            # that copy is the one to read, so an eager step in between
+            # (a batch of another shape) leaves its figures in it too
+            for k in ("q", "sqnorm"):
+                pair[3][k].copy_(ws[k])
+            ws = pair[3]
+        self.last_trust[gi] = ws["q"]
+        self.last_sqnorms[gi] = ws["sqnorm"]
+
+    # -- tensor-op path ------------------------------------------------------
+    def _trust(self, p, group, sqnorm):
+        """Writes (W, G) into `sqnorm` ([2]); returns q as a 0-dim tensor,
+        or None for a tensor that is not adapted. No host sync."""
+        state = self.state[p]
+        w = state["master"] if state.get("master") is not None else p.data
+        g = p.grad.float()
+        w2 = (w.float() * w.float()).sum()
+        g2 = (g * g).sum()
+        sqnorm[0] = w2
+        sqnorm[1] = g2
+        if p.ndim <= 1:
+            return None
+        nw, ng = w2.sqrt(), g2.sqrt()
+        q = group["trust_coef"] * nw / (
+            ng + group["weight_decay"] * nw + group["eps"])
+        return torch.where((w2 > 0) & (g2 > 0), q, torch.ones_like(q))
+
+    def _update_strided(self, group, strided):
+        gi = next(i for i, g in enumerate(self.param_groups) if g is group)
+        index = {id(p): i for i, p in enumerate(group["params"])}
+        for p, fresh in strided:
+            pi = index[id(p)]
+            q = self._trust(p, group, self.last_sqnorms[gi][pi])
+            if q is not None:
+                self.last_trust[gi][pi] = q
+            self._update_param(p, group, fresh, q)
+
+    def _fallback_group(self, group):
+        gi = next(i for i, g in enumerate(self.param_groups) if g is group)
+        n = len(group["params"])
+        device = group["params"][0].device
+        trust = torch.ones(n, dtype=torch.float32, device=device)
+        sqnorms = torch.zeros((n, 2), dtype=torch.float32, device=device)
+        for pi, p in enumerate(group["params"]):
+            if p.grad is None:
+                continue
+            fresh = self._init_state(p)
+            q = self._trust(p, group, sqnorms[pi])
+            if q is not None:
+                trust[pi] = q
+            self._update_param(p, group, fresh, q)
+        self.last_trust[gi] = trust
+        self.last_sqnorms[gi] = sqnorms

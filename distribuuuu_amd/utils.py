@@ -285,19 +285,33 @@ def set_lr(optimizer, new_lr):
 # ---------------------------------------------------------------------------
 def construct_optimizer(model):
     """SGD with momentum/nesterov/weight-decay; on GPU the fused multi-tensor
-    HIP step (ops.fused_sgd) replaces the per-tensor ATen step."""
-    from .ops.optim import HIPSGD
+    HIP step (ops.fused_sgd) replaces the per-tensor ATen step.
+    OPTIM.OPTIMIZER "lars" gives the same update with a layer-wise trust
+    ratio (ops.optim.HIPLARS), fused on GPU unless OPTIM.FUSED_SGD is off."""
+    from .ops.optim import HIPLARS, HIPSGD
 
-    use_fused = bool(cfg.OPTIM.FUSED_SGD) and torch.cuda.is_available()
-    klass = HIPSGD if use_fused else torch.optim.SGD
-    return klass(
-        model.parameters(),
+    name = cfg.OPTIM.OPTIMIZER
+    if name not in ("sgd", "lars"):
+        raise ValueError(
+            f"OPTIM.OPTIMIZER must be 'sgd' or 'lars', got {name!r}")
+    kwargs = dict(
         lr=cfg.OPTIM.BASE_LR,
         momentum=cfg.OPTIM.MOMENTUM,
         weight_decay=cfg.OPTIM.WEIGHT_DECAY,
         dampening=cfg.OPTIM.DAMPENING,
         nesterov=cfg.OPTIM.NESTEROV,
     )
+    if name == "lars":
+        return HIPLARS(
+            model.parameters(),
+            trust_coef=cfg.OPTIM.LARS_TRUST_COEF,
+            eps=cfg.OPTIM.LARS_EPS,
+            fused=bool(cfg.OPTIM.FUSED_SGD),
+            **kwargs,
+        )
+    use_fused = bool(cfg.OPTIM.FUSED_SGD) and torch.cuda.is_available()
+    klass = HIPSGD if use_fused else torch.optim.SGD
+    return klass(model.parameters(), **kwargs)
 
 
 # ---------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """Per-kernel micro-benchmarks on representative ResNet-50 shapes.
 
 Usage (on a GPU box): python tools/kbench.py [--deterministic] [group ...]
-Groups: bn conv wgrad pool ce sgd all
+Groups: bn conv wgrad pool gemm sgd all
 Prints achieved GB/s (memory-bound ops) or TF/s (MFMA ops) per shape.
 --deterministic: the wgrad rows time each shape in both modes, atomic and
 deterministic (docs/DETERMINISM.md), side by side.
@@ -152,6 +152,57 @@ def bench_gemm():
         print(f"gemm_nt {m}x{n}x{k}: {t*1e6:8.1f} us  {2.0*m*n*k/t/1e12:6.1f} TF")
 
 
+def _resnet50_shapes():
+    """Parameter shapes of torchvision-style ResNet-50 (161 tensors, 25.6M
+    elements): conv weights, BN weight/bias pairs, the classifier."""
+    shapes = [(64, 3, 7, 7), (64,), (64,)]
+    cin = 64
+    for width, blocks in ((64, 3), (128, 4), (256, 6), (512, 3)):
+        for b in range(blocks):
+            for k, c, r in ((width, cin, 1), (width, width, 3),
+                            (4 * width, width, 1)):
+                shapes += [(k, c, r, r), (k,), (k,)]
+            if b == 0:
+                shapes += [(4 * width, cin, 1, 1), (4 * width,), (4 * width,)]
+            cin = 4 * width
+    return shapes + [(1000, 2048), (1000,)]
+
+
+def bench_sgd():
+    from distribuuuu_amd.ops.optim import HIPLARS, HIPSGD
+
+    print("== optimizer step over ResNet-50's parameters (bf16 params and "
+          "grads, fp32 master + momentum) ==")
+    shapes = _resnet50_shapes()
+    numel = sum(torch.Size(s).numel() for s in shapes)
+    kw = dict(lr=0.0, momentum=0.9, weight_decay=5e-5, nesterov=True)
+    # bytes per element: grad 2 + master 4+4 + momentum 4+4 + param 2; the
+    # LARS norm pass reads master and grad once more
+    for name, klass, nbytes in (("sgd_step", HIPSGD, 20),
+                                ("lars_step", HIPLARS, 26)):
+        params = []
+        for s in shapes:
+            p = torch.randn(s, device=DEV).to(torch.bfloat16)
+            if len(s) == 4:
+                p = _cl(p)
+            p.grad = torch.randn_like(p)
+            params.append(p)
+        opt = klass(params, **kw)
+        opt.step()  # first step: state and the cached chunk table
+        group = opt.param_groups[0]
+        table = group["_hip_table_dev"]
+        tail = (0.0, 0.9, 0.0, 5e-5, True)  # lr, momentum, dampening, wd
+        if klass is HIPSGD:
+            t = timeit(lambda: e.sgd_step(table, *tail))
+        else:
+            ws = group["_hip_table_ws"]
+            t = timeit(lambda: e.lars_step(
+                table, ws["nchunks"], ws["part"], ws["sqnorm"], ws["q"],
+                *tail, 1e-3, 1e-8))
+        print(f"{name:10s} {len(shapes)} tensors {numel/1e6:5.1f}M elem "
+              f"{t*1e6:8.1f} us  {nbytes*numel/t/1e9:7.0f} GB/s")
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     deterministic = "--deterministic" in args
@@ -166,3 +217,5 @@ if __name__ == "__main__":
         bench_pool()
     if "gemm" in groups or "all" in groups:
         bench_gemm()
+    if "sgd" in groups or "all" in groups:
+        bench_sgd()

@@ -45,6 +45,8 @@ def parse_args():
     p.add_argument("--lr", type=float, default=0.0)
     p.add_argument("--print-freq", type=int, default=30)
     p.add_argument("--im-size", type=int, default=224)
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
+                   help="OPTIM.OPTIMIZER: fused SGD-momentum, or LARS on it")
     p.add_argument("--modes", default="eager,captured",
                    help="comma list; one mode alone is for profiling it")
     return p.parse_args()
@@ -75,6 +77,7 @@ def main():
     cfg.TRAIN.BATCH_SIZE = batch
     cfg.TRAIN.PRINT_FREQ = args.print_freq
     cfg.OPTIM.BASE_LR = args.lr
+    cfg.OPTIM.OPTIMIZER = args.optimizer
     cfg.OPTIM.WARMUP_EPOCHS = 0
     cfg.OUT_DIR = os.environ.get("BENCH_OUT_DIR", "/tmp/bench_out")
     cfg.freeze()
@@ -141,6 +144,7 @@ def main():
         "dtype": "bf16" if use_bf16 else "fp32",
         "print_freq": args.print_freq,
         "lr": args.lr,
+        "optimizer": args.optimizer,
         "weights_finite": finite,
         "runner": runner.stats,
     }))
