@@ -40,7 +40,24 @@ std::vector<at::Tensor> bn_bwd(at::Tensor gy, at::Tensor x,
                                c10::optional<at::Tensor> mask);
 std::vector<at::Tensor> bn_apply_act_mask(at::Tensor x, at::Tensor scale,
                                           at::Tensor shift, int64_t act,
-                                          at::Tensor res);
+                                          at::Tensor res,
+                                          c10::optional<at::Tensor> res_scale,
+                                          c10::optional<at::Tensor> res_shift);
+std::vector<at::Tensor> bn_act_maxpool_fwd(at::Tensor x, at::Tensor scale,
+                                           at::Tensor shift, int64_t act);
+at::Tensor bn_pool_bwd_stats(at::Tensor gpool, at::Tensor idx, at::Tensor x,
+                             at::Tensor scale, at::Tensor shift, int64_t act);
+std::vector<at::Tensor> bn_pool_bwd_apply(at::Tensor gpool, at::Tensor idx,
+                                          at::Tensor x, at::Tensor mean,
+                                          at::Tensor rstd, at::Tensor gamma,
+                                          at::Tensor scale, at::Tensor shift,
+                                          at::Tensor sums, double total_count,
+                                          int64_t act, bool training);
+std::vector<at::Tensor> bn_pool_bwd(at::Tensor gpool, at::Tensor idx,
+                                    at::Tensor x, at::Tensor mean,
+                                    at::Tensor rstd, at::Tensor gamma,
+                                    at::Tensor scale, at::Tensor shift,
+                                    int64_t act, bool training);
 at::Tensor bn_apply_act_pad(at::Tensor x, at::Tensor scale, at::Tensor shift,
                             int64_t act, int64_t ph, int64_t pw);
 std::vector<at::Tensor> bn_bwd_pad(at::Tensor gy, at::Tensor x,
@@ -170,7 +187,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("training") = true, py::arg("part") = py::none());
   m.def("bn_apply_act", &bn_apply_act, py::arg("x"), py::arg("scale"),
         py::arg("shift"), py::arg("act"), py::arg("res") = py::none());
-  m.def("bn_apply_act_mask", &bn_apply_act_mask);
+  m.def("bn_apply_act_mask", &bn_apply_act_mask, py::arg("x"),
+        py::arg("scale"), py::arg("shift"), py::arg("act"), py::arg("res"),
+        py::arg("res_scale") = py::none(), py::arg("res_shift") = py::none());
+  m.def("bn_act_maxpool_fwd", &bn_act_maxpool_fwd);
+  m.def("bn_pool_bwd_stats", &bn_pool_bwd_stats);
+  m.def("bn_pool_bwd_apply", &bn_pool_bwd_apply);
+  m.def("bn_pool_bwd", &bn_pool_bwd);
   m.def("bn_apply_act_pad", &bn_apply_act_pad);
   m.def("bn_bwd_pad", &bn_bwd_pad);
   m.def("bn_bwd_stats", &bn_bwd_stats, py::arg("gy"), py::arg("x"),

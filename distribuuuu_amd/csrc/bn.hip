@@ -47,6 +47,16 @@ DEV_INLINE float act_grad(float z, int act) {
   }
 }
 
+// gx = P1*g + P3*x + P2 as mul, fma, add, kept from further contraction.
+// Every dx kernel that must agree bit for bit (bn_bwd_dx_kernel and the
+// pooled-gradient bn_pool_bwd_dx_kernel) goes through this one spelling:
+// left to the compiler, the fusion it picks depends on how g was produced
+// (loaded vs. summed from gathered taps) and the last bit moves.
+DEV_INLINE float bn_dx_value(float a1, float a2, float a3, float g, float xv) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(a3, xv, a1 * g) + a2;
+}
+
 DEV_INLINE int p2_floor(int v) { return 1 << (31 - __builtin_clz(v)); }
 
 // ---- fwd stage 1: per-channel sum / sum-of-squares partials ----------------
@@ -245,13 +255,20 @@ __global__ void bn_eval_prep_kernel(const float* __restrict__ running_mean,
 // EMITMASK (HAS_RES relu only): one act'(z) bit per element, a byte per
 // V-pack at [row * cpacks + cp] — the backward kernels then skip the res
 // stream AND the z recompute (docs/ARCHITECTURE.md round-2 status).
-template <typename T, bool HAS_RES, bool EMITMASK = false>
+// RESBN (EMITMASK only): res is the RAW output of the shortcut conv and the
+// shortcut BN (no act) is applied here, rounded to T before the add — the
+// value the standalone apply used to store — so the identity tensor of a
+// downsample block is never written or read back.
+template <typename T, bool HAS_RES, bool EMITMASK = false, bool RESBN = false>
 __global__ __launch_bounds__(256, 2) void bn_apply_kernel(
     const T* __restrict__ x, const float* __restrict__ scale,
     const float* __restrict__ shift, const T* __restrict__ res,
     T* __restrict__ y, int64_t rows, int C, int64_t rows_per_block, int act,
-    unsigned char* __restrict__ mask = nullptr) {
+    unsigned char* __restrict__ mask = nullptr,
+    const float* __restrict__ res_scale = nullptr,
+    const float* __restrict__ res_shift = nullptr) {
   static_assert(!(EMITMASK && !HAS_RES), "mask emission is for residual BNs");
+  static_assert(!(RESBN && !EMITMASK), "shortcut-BN apply rides the mask path");
   constexpr int V = 16 / sizeof(T);
   using P = Pack<T, V>;
   const int cpacks = C / V;
@@ -266,11 +283,15 @@ __global__ __launch_bounds__(256, 2) void bn_apply_kernel(
   const P* rp = reinterpret_cast<const P*>(res);
   P* yp = reinterpret_cast<P*>(y);
   for (int cp = cp0; cp < cpacks; cp += ncp) {
-    float sc[V], sh[V];
+    float sc[V], sh[V], rsc[V], rsh[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       sc[j] = scale[cp * V + j];
       sh[j] = shift[cp * V + j];
+      if (RESBN) {
+        rsc[j] = res_scale[cp * V + j];
+        rsh[j] = res_shift[cp * V + j];
+      }
     }
     if (!active) continue;
     int64_t row = row0 + rl;
@@ -294,7 +315,10 @@ __global__ __launch_bounds__(256, 2) void bn_apply_kernel(
 #pragma unroll
         for (int j = 0; j < V; ++j) {
           float z = to_f32(px4[u].v[j]) * sc[j] + sh[j];
-          if (HAS_RES) z += to_f32(pr4[u].v[j]);
+          if (RESBN)
+            z += to_f32(from_f32<T>(to_f32(pr4[u].v[j]) * rsc[j] + rsh[j]));
+          else if (HAS_RES)
+            z += to_f32(pr4[u].v[j]);
           if (EMITMASK && z > 0.f) mb |= 1u << j;
           px4[u].v[j] = from_f32<T>(act_apply(z, act));
         }
@@ -313,7 +337,10 @@ __global__ __launch_bounds__(256, 2) void bn_apply_kernel(
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         float z = to_f32(px.v[j]) * sc[j] + sh[j];
-        if (HAS_RES) z += to_f32(pr.v[j]);
+        if (RESBN)
+          z += to_f32(from_f32<T>(to_f32(pr.v[j]) * rsc[j] + rsh[j]));
+        else if (HAS_RES)
+          z += to_f32(pr.v[j]);
         if (EMITMASK && z > 0.f) mb |= 1u << j;
         px.v[j] = from_f32<T>(act_apply(z, act));
       }
@@ -604,7 +631,7 @@ __global__ __launch_bounds__(256, 2) void bn_bwd_dx_kernel(
             g *= act_grad(z, ACT);
           }
           if (HAS_RES) orr.v[j] = from_f32<T>(g);
-          ox.v[j] = from_f32<T>(a1[j] * g + a3[j] * xv + a2[j]);
+          ox.v[j] = from_f32<T>(bn_dx_value(a1[j], a2[j], a3[j], g, xv));
         }
         oq[u * rstep] = ox;
         if (HAS_RES) orq[u * rstep] = orr;
@@ -636,7 +663,7 @@ __global__ __launch_bounds__(256, 2) void bn_bwd_dx_kernel(
           g *= act_grad(z, ACT);
         }
         if (HAS_RES) orr.v[j] = from_f32<T>(g);
-        ox.v[j] = from_f32<T>(a1[j] * g + a3[j] * xv + a2[j]);
+        ox.v[j] = from_f32<T>(bn_dx_value(a1[j], a2[j], a3[j], g, xv));
       }
       oq[0] = ox;
       if (HAS_RES) orq[0] = orr;
@@ -1258,11 +1285,26 @@ __global__ __launch_bounds__(256, 2) void bn_bwd_dx_pad_kernel(
 // recompute. Returns {y, mask}.
 std::vector<at::Tensor> bn_apply_act_mask(at::Tensor x, at::Tensor scale,
                                           at::Tensor shift, int64_t act,
-                                          at::Tensor res) {
+                                          at::Tensor res,
+                                          c10::optional<at::Tensor> res_scale,
+                                          c10::optional<at::Tensor> res_shift) {
   CHECK_GPU(x);
   check_nhwc(x, "x");
+  check_nhwc(res, "res");
   TORCH_CHECK(act == 1, "mask emission: relu only");
+  TORCH_CHECK(res.sizes() == x.sizes() && res.scalar_type() == x.scalar_type(),
+              "bn_apply_act_mask: res must match x");
+  // res_scale/res_shift given: res is the raw shortcut-conv output and its
+  // BN is applied in the same pass (downsample blocks)
+  const bool resbn = res_scale.has_value();
+  TORCH_CHECK(resbn == res_shift.has_value(),
+              "bn_apply_act_mask: res_scale and res_shift go together");
   const int C = x.size(1);
+  if (resbn)
+    TORCH_CHECK(res_scale->numel() == C && res_shift->numel() == C &&
+                    res_scale->scalar_type() == at::kFloat &&
+                    res_shift->scalar_type() == at::kFloat,
+                "bn_apply_act_mask: res_scale/res_shift are fp32 [C]");
   auto y = at::empty_like(x);
   at::Tensor mask;
   DISPATCH_FLOAT_AND_BF16(x.scalar_type(), "bn_apply_act_mask", [&] {
@@ -1274,13 +1316,24 @@ std::vector<at::Tensor> bn_apply_act_mask(at::Tensor x, at::Tensor scale,
     const int nrl = std::max(256 / cpacks, 1);
     const int64_t rpb = pick_rows_per_block(rows, nrl);
     const int rgrid = (int)ceil_div(rows, rpb);
-    hipLaunchKernelGGL((bn_apply_kernel<scalar_t, true, true>), dim3(rgrid),
-                       dim3(256), 0, cur_stream(),
-                       (const scalar_t*)x.data_ptr(),
-                       scale.data_ptr<float>(), shift.data_ptr<float>(),
-                       (const scalar_t*)res.data_ptr(),
-                       (scalar_t*)y.data_ptr(), rows, C, rpb, (int)act,
-                       (unsigned char*)mask.data_ptr());
+    if (resbn)
+      hipLaunchKernelGGL((bn_apply_kernel<scalar_t, true, true, true>),
+                         dim3(rgrid), dim3(256), 0, cur_stream(),
+                         (const scalar_t*)x.data_ptr(),
+                         scale.data_ptr<float>(), shift.data_ptr<float>(),
+                         (const scalar_t*)res.data_ptr(),
+                         (scalar_t*)y.data_ptr(), rows, C, rpb, (int)act,
+                         (unsigned char*)mask.data_ptr(),
+                         res_scale->data_ptr<float>(),
+                         res_shift->data_ptr<float>());
+    else
+      hipLaunchKernelGGL((bn_apply_kernel<scalar_t, true, true>), dim3(rgrid),
+                         dim3(256), 0, cur_stream(),
+                         (const scalar_t*)x.data_ptr(),
+                         scale.data_ptr<float>(), shift.data_ptr<float>(),
+                         (const scalar_t*)res.data_ptr(),
+                         (scalar_t*)y.data_ptr(), rows, C, rpb, (int)act,
+                         (unsigned char*)mask.data_ptr());
   });
   return {y, mask};
 }
@@ -1552,4 +1605,691 @@ std::vector<at::Tensor> bn_bwd(at::Tensor gy, at::Tensor x,
                         rows, C, rpb, (int)act, rgrid, stream, maskp);
   });
   return {gx, gw, gb, gres};
+}
+
+// ===========================================================================
+// Stem fusion: BN(+act) -> maxpool(3, 2, 1) without the full-size BN output
+// ===========================================================================
+// fwd:  bn_act_maxpool_fwd_kernel reads the raw conv output once and writes
+//       the pooled tensor + window-local argmax bytes; every tap is
+//       normalised, activated and ROUNDED TO T before the strict-> compare,
+//       so pooled values and argmax equal bn_apply -> maxpool_fwd bit for bit.
+// bwd:  bn_pool_bwd_reduce_kernel / bn_pool_bwd_dx_kernel are the
+//       bn_bwd_reduce / bn_bwd_dx <T, false, ACT> row walks whose g is
+//       gathered from the pooled gradient (up to 2x2 windows, k3s2 order,
+//       rounded to T like the tensor maxpool_bwd used to store). Same grid,
+//       same per-thread row order, same LDS tree => same partial matrix.
+namespace {
+
+// q = m / d for m * d < 2^47 with magic = 2^47 / d + 1
+DEV_INLINE int magic_div(int m, unsigned long long magic) {
+  return (int)(((unsigned long long)(unsigned)m * magic) >> 47);
+}
+inline unsigned long long magic_of(int64_t d) {
+  return ((1ULL << 47) / (unsigned long long)d) + 1;
+}
+
+template <typename T, int ACT>
+__global__ __launch_bounds__(256) void bn_act_maxpool_fwd_kernel(
+    const T* __restrict__ x, const float* __restrict__ scale,
+    const float* __restrict__ shift, T* __restrict__ y,
+    unsigned char* __restrict__ idx, int H, int W, int C, int Ho, int Wo,
+    unsigned long long magic_cp) {
+  constexpr int V = 16 / sizeof(T);
+  using P = Pack<T, V>;
+  const int cpacks = C / V;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Wo * cpacks) return;
+  const int orow = blockIdx.y;  // n * Ho + ho, block-uniform
+  const int n = orow / Ho, ho = orow - n * Ho;
+  const int wo = magic_div(i, magic_cp);
+  const int cp = i - wo * cpacks;
+  const int h0 = 2 * ho - 1, w0 = 2 * wo - 1;
+  // the centre tap (kh = kw = 1) is always in bounds
+  const bool hok[3] = {h0 >= 0, true, h0 + 2 < H};
+  const bool wok[3] = {w0 >= 0, true, w0 + 2 < W};
+  const P* xc = reinterpret_cast<const P*>(x) +
+                (((int64_t)n * H + h0 + 1) * W + w0 + 1) * cpacks + cp;
+  const int dh = W * cpacks;
+  P tap[9];
+#pragma unroll
+  for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw)
+      if (hok[kh] && wok[kw])
+        tap[kh * 3 + kw] = xc[(kh - 1) * dh + (kw - 1) * cpacks];
+  float sc[V], sh[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    sc[j] = scale[cp * V + j];
+    sh[j] = shift[cp * V + j];
+  }
+  // argmax kept one int per element and packed to bytes once at the end
+  // (byte-wise updates cost several ALU ops per tap and element, and this
+  // kernel is ALU-bound before it is bandwidth-bound)
+  float best[V];
+  unsigned bidx[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    best[j] = -INFINITY;
+    bidx[j] = 0;
+  }
+#pragma unroll
+  for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw)
+      if (hok[kh] && wok[kw]) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          const float z = to_f32(tap[kh * 3 + kw].v[j]) * sc[j] + sh[j];
+          const float v = to_f32(from_f32<T>(act_apply(z, ACT)));
+          if (v > best[j]) {
+            best[j] = v;
+            bidx[j] = kh * 3 + kw;
+          }
+        }
+      }
+  const int64_t out = ((int64_t)orow * Wo + wo) * C + cp * V;
+  P py;
+#pragma unroll
+  for (int j = 0; j < V; ++j) py.v[j] = from_f32<T>(best[j]);
+  *reinterpret_cast<P*>(y + out) = py;
+  unsigned words[V / 4];
+#pragma unroll
+  for (int q = 0; q < V / 4; ++q)
+    words[q] = bidx[4 * q] | (bidx[4 * q + 1] << 8) |
+               (bidx[4 * q + 2] << 16) | (bidx[4 * q + 3] << 24);
+  if (V == 8)
+    *reinterpret_cast<uint2*>(idx + out) = make_uint2(words[0], words[V / 4 - 1]);
+  else
+    *reinterpret_cast<unsigned int*>(idx + out) = words[0];
+}
+
+// argmax bytes of one V-pack as a single word
+template <int V>
+struct IdxWord {
+  using type = unsigned int;
+};
+template <>
+struct IdxWord<8> {
+  using type = unsigned long long;
+};
+
+// (n, h, w) of a dense row plus the carry constants of a fixed row stride
+struct RowWalk {
+  int n, h, w;
+  int sdn, sdh, sdw;
+};
+
+DEV_INLINE RowWalk row_walk_init(int row, int nrl, int H, int W,
+                                 unsigned long long magicHW,
+                                 unsigned long long magicW) {
+  RowWalk r;
+  const int HW = H * W;
+  r.n = magic_div(row, magicHW);
+  int rem = row - r.n * HW;
+  r.h = magic_div(rem, magicW);
+  r.w = rem - r.h * W;
+  r.sdn = magic_div(nrl, magicHW);
+  rem = nrl - r.sdn * HW;
+  r.sdh = magic_div(rem, magicW);
+  r.sdw = rem - r.sdh * W;
+  return r;
+}
+
+// sdw < W and sdh < H, so one conditional subtract per digit is enough
+DEV_INLINE void row_walk_step(RowWalk& r, int H, int W) {
+  r.w += r.sdw;
+  if (r.w >= W) {
+    r.w -= W;
+    ++r.h;
+  }
+  r.h += r.sdh;
+  if (r.h >= H) {
+    r.h -= H;
+    ++r.n;
+  }
+  r.n += r.sdn;
+}
+
+// Issue the up-to-four (gpool, idx) loads of input position (n, h, w); slots
+// that do not exist are neither loaded nor summed. Returns the tap code
+// (h & 1) * 2 + (w & 1) + 4 * w2 + 8 * h2 (w2 / h2: a second window column /
+// row exists).
+template <typename T, int V>
+DEV_INLINE int pool_taps_load(const Pack<T, V>* __restrict__ gp,
+                              const typename IdxWord<V>::type* __restrict__ ip,
+                              const RowWalk& r, int Ho, int Wo, int cpacks,
+                              int cp, Pack<T, V> (&g)[4],
+                              typename IdxWord<V>::type (&bi)[4]) {
+  const int ho0 = r.h >> 1, wo0 = r.w >> 1;
+  const bool h2 = (r.h & 1) && ho0 + 1 < Ho;
+  const bool w2 = (r.w & 1) && wo0 + 1 < Wo;
+  const int64_t o = (int64_t)((r.n * Ho + ho0) * Wo + wo0) * cpacks + cp;
+  const int64_t dW = (int64_t)Wo * cpacks;
+  g[0] = gp[o];
+  bi[0] = ip[o];
+  if (w2) {
+    g[1] = gp[o + cpacks];
+    bi[1] = ip[o + cpacks];
+  }
+  if (h2) {
+    g[2] = gp[o + dW];
+    bi[2] = ip[o + dW];
+    if (w2) {
+      g[3] = gp[o + dW + cpacks];
+      bi[3] = ip[o + dW + cpacks];
+    }
+  }
+  return (r.h & 1) * 2 + (r.w & 1) + (w2 ? 4 : 0) + (h2 ? 8 : 0);
+}
+
+template <typename T, int V>
+DEV_INLINE void pool_tap_add(const Pack<T, V>& g,
+                             typename IdxWord<V>::type bi, unsigned want,
+                             float (&a)[V]) {
+#pragma unroll
+  for (int j = 0; j < V; ++j)
+    if ((unsigned)((bi >> (8 * j)) & 0xff) == want) a[j] += to_f32(g.v[j]);
+}
+
+// fp32 sum in (ho0,wo0), (ho0,wo1), (ho1,wo0), (ho1,wo1) order, rounded to T
+// and widened again: the value maxpool_bwd_k3s2_kernel stores.
+template <typename T, int V>
+DEV_INLINE void pool_taps_sum(const Pack<T, V> (&g)[4],
+                              const typename IdxWord<V>::type (&bi)[4],
+                              int code, float (&out)[V]) {
+  const unsigned kh0 = ((code >> 1) & 1) + 1, kw0 = (code & 1) + 1;
+  const bool w2 = code & 4, h2 = code & 8;
+  float a[V] = {};
+  pool_tap_add<T, V>(g[0], bi[0], kh0 * 3 + kw0, a);
+  if (w2) pool_tap_add<T, V>(g[1], bi[1], kh0 * 3, a);
+  if (h2) {
+    pool_tap_add<T, V>(g[2], bi[2], kw0, a);
+    if (w2) pool_tap_add<T, V>(g[3], bi[3], 0u, a);
+  }
+#pragma unroll
+  for (int j = 0; j < V; ++j) out[j] = to_f32(from_f32<T>(a[j]));
+}
+
+// Row-lane role of a thread. bn_bwd hands row lane q = tid / ncp the rows
+// row0 + q + k * nrl; here the first half of the q range takes the even row
+// lanes and the second half the odd ones. Roles, rows per role and LDS slots
+// are unchanged (so the partial matrix is), but with W and nrl even a wave
+// then holds columns of ONE parity and the w2 / h2 branches above skip whole
+// waves instead of diverging in every one.
+DEV_INLINE int pool_row_lane(int q, int nrl) {
+  if (q >= nrl || nrl < 2) return q;
+  const int half = nrl >> 1;
+  return q < half ? 2 * q : 2 * (q - half) + 1;
+}
+
+constexpr int POOL_U = 2;  // rows in flight per thread (4 spills)
+
+template <typename T, int ACT>
+__global__ __launch_bounds__(256, 2) void bn_pool_bwd_reduce_kernel(
+    const T* __restrict__ gpool, const unsigned char* __restrict__ idx,
+    const T* __restrict__ x, const float* __restrict__ scale,
+    const float* __restrict__ shift, float* __restrict__ part, int64_t rows,
+    int C, int H, int W, int Ho, int Wo, int64_t rows_per_block,
+    unsigned long long magicHW, unsigned long long magicW) {
+  constexpr int V = 16 / sizeof(T);
+  using P = Pack<T, V>;
+  using IW = typename IdxWord<V>::type;
+  __shared__ float red[256 * 2 * (16 / sizeof(T) > 8 ? 16 / sizeof(T) : 8)];
+  const int cpacks = C / V;
+  const int ncp = min(cpacks, (int)blockDim.x);
+  const int nrl = p2_floor(blockDim.x / ncp);
+  const int cp0 = threadIdx.x % ncp;
+  const int rl = pool_row_lane(threadIdx.x / ncp, nrl);
+  const bool active = rl < nrl;
+  const int64_t row0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t row1 = min(row0 + rows_per_block, rows);
+  const P* gp = reinterpret_cast<const P*>(gpool);
+  const IW* ip = reinterpret_cast<const IW*>(idx);
+  const P* xp = reinterpret_cast<const P*>(x);
+  for (int cp = cp0; cp < cpacks; cp += ncp) {
+    float sc[V], sh[V];
+    if (ACT != 0) {
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        sc[j] = scale[cp * V + j];
+        sh[j] = shift[cp * V + j];
+      }
+    }
+    float accg[V] = {}, accgx[V] = {};
+    if (active) {
+      int64_t row = row0 + rl;
+      const int64_t rstep = (int64_t)nrl * cpacks;
+      const P* xq = xp + row * cpacks + cp;
+      RowWalk rw = row_walk_init((int)row, nrl, H, W, magicHW, magicW);
+      for (; row + (POOL_U - 1) * (int64_t)nrl < row1;
+           row += POOL_U * (int64_t)nrl) {
+        P px4[POOL_U], pg4[POOL_U][4];
+        IW bi4[POOL_U][4];
+        int par4[POOL_U];
+#pragma unroll
+        for (int u = 0; u < POOL_U; ++u) {
+          px4[u] = xq[u * rstep];
+          par4[u] = pool_taps_load<T, V>(gp, ip, rw, Ho, Wo, cpacks, cp,
+                                         pg4[u], bi4[u]);
+          row_walk_step(rw, H, W);
+        }
+        xq += POOL_U * rstep;
+#pragma unroll
+        for (int u = 0; u < POOL_U; ++u) {
+          float gv[V];
+          pool_taps_sum<T, V>(pg4[u], bi4[u], par4[u], gv);
+#pragma unroll
+          for (int j = 0; j < V; ++j) {
+            float xv = to_f32(px4[u].v[j]);
+            float g = gv[j];
+            if (ACT != 0) {
+              float z = xv * sc[j] + sh[j];
+              g *= act_grad(z, ACT);
+            }
+            accg[j] += g;
+            accgx[j] += g * xv;
+          }
+        }
+      }
+      for (; row < row1; row += nrl) {
+        P px = xq[0], pg[4];
+        IW bi[4];
+        xq += rstep;
+        const int par =
+            pool_taps_load<T, V>(gp, ip, rw, Ho, Wo, cpacks, cp, pg, bi);
+        row_walk_step(rw, H, W);
+        float gv[V];
+        pool_taps_sum<T, V>(pg, bi, par, gv);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          float xv = to_f32(px.v[j]);
+          float g = gv[j];
+          if (ACT != 0) {
+            float z = xv * sc[j] + sh[j];
+            g *= act_grad(z, ACT);
+          }
+          accg[j] += g;
+          accgx[j] += g * xv;
+        }
+      }
+    }
+    float* slot = &red[(rl * ncp + cp0) * 2 * V];
+    if (active) {
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        slot[j] = accg[j];
+        slot[V + j] = accgx[j];
+      }
+    }
+    __syncthreads();
+    for (int st = nrl >> 1; st > 0; st >>= 1) {
+      if (active && rl < st) {
+        const float* other = &red[((rl + st) * ncp + cp0) * 2 * V];
+#pragma unroll
+        for (int j = 0; j < 2 * V; ++j) slot[j] += other[j];
+      }
+      __syncthreads();
+    }
+    if (active && rl == 0) {
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        part[(int64_t)blockIdx.x * 2 * C + cp * V + j] = slot[j];
+        part[(int64_t)blockIdx.x * 2 * C + C + cp * V + j] = slot[V + j];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+template <typename T, int ACT>
+__global__ __launch_bounds__(256, 2) void bn_pool_bwd_dx_kernel(
+    const T* __restrict__ gpool, const unsigned char* __restrict__ idx,
+    const T* __restrict__ x, const float* __restrict__ scale,
+    const float* __restrict__ shift, const float* __restrict__ P1c,
+    const float* __restrict__ P2c, const float* __restrict__ P3c,
+    T* __restrict__ gx, int64_t rows, int C, int H, int W, int Ho, int Wo,
+    int64_t rows_per_block, unsigned long long magicHW,
+    unsigned long long magicW) {
+  constexpr int V = 16 / sizeof(T);
+  using P = Pack<T, V>;
+  using IW = typename IdxWord<V>::type;
+  const int cpacks = C / V;
+  const int ncp = min(cpacks, (int)blockDim.x);
+  const int nrl = p2_floor(blockDim.x / ncp);
+  const int cp0 = threadIdx.x % ncp;
+  const int rl = pool_row_lane(threadIdx.x / ncp, nrl);
+  const bool active = rl < nrl;
+  const int64_t row0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t row1 = min(row0 + rows_per_block, rows);
+  const P* gp = reinterpret_cast<const P*>(gpool);
+  const IW* ip = reinterpret_cast<const IW*>(idx);
+  const P* xp = reinterpret_cast<const P*>(x);
+  P* oxp = reinterpret_cast<P*>(gx);
+  for (int cp = cp0; cp < cpacks; cp += ncp) {
+    float sc[V], sh[V], a1[V], a2[V], a3[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const int cc = cp * V + j;
+      a1[j] = P1c[cc];
+      a2[j] = P2c[cc];
+      a3[j] = P3c[cc];
+      if (ACT != 0) {
+        sc[j] = scale[cc];
+        sh[j] = shift[cc];
+      }
+    }
+    if (!active) continue;
+    int64_t row = row0 + rl;
+    const int64_t rstep = (int64_t)nrl * cpacks;
+    const P* xq = xp + row * cpacks + cp;
+    P* oq = oxp + row * cpacks + cp;
+    RowWalk rw = row_walk_init((int)row, nrl, H, W, magicHW, magicW);
+    for (; row + (POOL_U - 1) * (int64_t)nrl < row1;
+         row += POOL_U * (int64_t)nrl) {
+      P px4[POOL_U], pg4[POOL_U][4];
+      IW bi4[POOL_U][4];
+      int par4[POOL_U];
+#pragma unroll
+      for (int u = 0; u < POOL_U; ++u) {
+        px4[u] = xq[u * rstep];
+        par4[u] = pool_taps_load<T, V>(gp, ip, rw, Ho, Wo, cpacks, cp,
+                                       pg4[u], bi4[u]);
+        row_walk_step(rw, H, W);
+      }
+      xq += POOL_U * rstep;
+#pragma unroll
+      for (int u = 0; u < POOL_U; ++u) {
+        float gv[V];
+        pool_taps_sum<T, V>(pg4[u], bi4[u], par4[u], gv);
+        P ox;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          float xv = to_f32(px4[u].v[j]);
+          float g = gv[j];
+          if (ACT != 0) {
+            float z = xv * sc[j] + sh[j];
+            g *= act_grad(z, ACT);
+          }
+          ox.v[j] = from_f32<T>(bn_dx_value(a1[j], a2[j], a3[j], g, xv));
+        }
+        oq[u * rstep] = ox;
+      }
+      oq += POOL_U * rstep;
+    }
+    for (; row < row1; row += nrl) {
+      P px = xq[0], pg[4];
+      IW bi[4];
+      xq += rstep;
+      const int par =
+          pool_taps_load<T, V>(gp, ip, rw, Ho, Wo, cpacks, cp, pg, bi);
+      row_walk_step(rw, H, W);
+      float gv[V];
+      pool_taps_sum<T, V>(pg, bi, par, gv);
+      P ox;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        float xv = to_f32(px.v[j]);
+        float g = gv[j];
+        if (ACT != 0) {
+          float z = xv * sc[j] + sh[j];
+          g *= act_grad(z, ACT);
+        }
+        ox.v[j] = from_f32<T>(bn_dx_value(a1[j], a2[j], a3[j], g, xv));
+      }
+      oq[0] = ox;
+      oq += rstep;
+    }
+  }
+}
+
+// shape checks shared by the three backward entries; returns {Ho, Wo}
+std::pair<int, int> check_pool_bwd_args(const at::Tensor& gpool,
+                                        const at::Tensor& idx,
+                                        const at::Tensor& x) {
+  CHECK_GPU(gpool);
+  CHECK_GPU(idx);
+  CHECK_GPU(x);
+  check_nhwc(gpool, "gpool");
+  check_nhwc(idx, "idx");
+  check_nhwc(x, "x");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  TORCH_CHECK(gpool.size(0) == N && gpool.size(1) == C &&
+                  gpool.size(2) == Ho && gpool.size(3) == Wo,
+              "bn_pool_bwd: gpool is not the (3, 2, 1) pooling of x");
+  TORCH_CHECK(idx.sizes() == gpool.sizes() && idx.scalar_type() == at::kByte,
+              "bn_pool_bwd: idx must be uint8 with gpool's shape");
+  TORCH_CHECK(gpool.scalar_type() == x.scalar_type(),
+              "bn_pool_bwd: gpool/x dtype mismatch");
+  const int64_t rows = N * H * W;
+  // 32-bit row split and exact magic division (m * d < 2^47)
+  TORCH_CHECK(rows + 256 < (1LL << 31) &&
+                  (rows + 256) * (H * W) < (1LL << 47),
+              "bn_pool_bwd: tensor too large for the row split");
+  return {(int)Ho, (int)Wo};
+}
+
+template <typename scalar_t>
+void launch_bn_act_maxpool_fwd(const at::Tensor& x, const at::Tensor& scale,
+                               const at::Tensor& shift, at::Tensor& y,
+                               at::Tensor& idx, int N, int H, int W, int C,
+                               int Ho, int Wo, int act, hipStream_t stream) {
+  constexpr int V = 16 / sizeof(scalar_t);
+  const int cpacks = C / V;
+  const dim3 grid((unsigned)ceil_div((int64_t)Wo * cpacks, 256), N * Ho);
+  const unsigned long long mcp = magic_of(cpacks);
+#define BMP_CASE(A)                                                          \
+  hipLaunchKernelGGL((bn_act_maxpool_fwd_kernel<scalar_t, A>), grid,         \
+                     dim3(256), 0, stream, (const scalar_t*)x.data_ptr(),    \
+                     scale.data_ptr<float>(), shift.data_ptr<float>(),       \
+                     (scalar_t*)y.data_ptr(), idx.data_ptr<unsigned char>(), \
+                     H, W, C, Ho, Wo, mcp)
+  switch (act) {
+    case 0: BMP_CASE(0); break;
+    case 1: BMP_CASE(1); break;
+    default: TORCH_CHECK(false, "fused BN + maxpool: act none or relu only");
+  }
+#undef BMP_CASE
+}
+
+template <typename scalar_t>
+void launch_pool_bwd_reduce(const at::Tensor& gpool, const at::Tensor& idx,
+                            const at::Tensor& x, const at::Tensor& scale,
+                            const at::Tensor& shift, at::Tensor& part,
+                            int64_t rows, int C, int H, int W, int Ho, int Wo,
+                            int64_t rpb, int act, int rgrid,
+                            hipStream_t stream) {
+  const unsigned long long mHW = magic_of((int64_t)H * W), mW = magic_of(W);
+#define PBR_CASE(A)                                                          \
+  hipLaunchKernelGGL((bn_pool_bwd_reduce_kernel<scalar_t, A>), dim3(rgrid),  \
+                     dim3(256), 0, stream,                                   \
+                     (const scalar_t*)gpool.data_ptr(),                      \
+                     idx.data_ptr<unsigned char>(),                          \
+                     (const scalar_t*)x.data_ptr(), scale.data_ptr<float>(), \
+                     shift.data_ptr<float>(), part.data_ptr<float>(), rows,  \
+                     C, H, W, Ho, Wo, rpb, mHW, mW)
+  switch (act) {
+    case 0: PBR_CASE(0); break;
+    case 1: PBR_CASE(1); break;
+    default: TORCH_CHECK(false, "fused BN + maxpool: act none or relu only");
+  }
+#undef PBR_CASE
+}
+
+template <typename scalar_t>
+void launch_pool_bwd_dx(const at::Tensor& gpool, const at::Tensor& idx,
+                        const at::Tensor& x, const at::Tensor& scale,
+                        const at::Tensor& shift, const at::Tensor& P1,
+                        const at::Tensor& P2, const at::Tensor& P3,
+                        at::Tensor& gx, int64_t rows, int C, int H, int W,
+                        int Ho, int Wo, int64_t rpb, int act, int rgrid,
+                        hipStream_t stream) {
+  const unsigned long long mHW = magic_of((int64_t)H * W), mW = magic_of(W);
+#define PBD_CASE(A)                                                          \
+  hipLaunchKernelGGL((bn_pool_bwd_dx_kernel<scalar_t, A>), dim3(rgrid),      \
+                     dim3(256), 0, stream,                                   \
+                     (const scalar_t*)gpool.data_ptr(),                      \
+                     idx.data_ptr<unsigned char>(),                          \
+                     (const scalar_t*)x.data_ptr(), scale.data_ptr<float>(), \
+                     shift.data_ptr<float>(), P1.data_ptr<float>(),          \
+                     P2.data_ptr<float>(), P3.data_ptr<float>(),             \
+                     (scalar_t*)gx.data_ptr(), rows, C, H, W, Ho, Wo, rpb,   \
+                     mHW, mW)
+  switch (act) {
+    case 0: PBD_CASE(0); break;
+    case 1: PBD_CASE(1); break;
+    default: TORCH_CHECK(false, "fused BN + maxpool: act none or relu only");
+  }
+#undef PBD_CASE
+}
+
+}  // namespace
+
+// y_pooled, idx = maxpool3x3s2p1(act(x*scale + shift)) in one pass over x.
+std::vector<at::Tensor> bn_act_maxpool_fwd(at::Tensor x, at::Tensor scale,
+                                           at::Tensor shift, int64_t act) {
+  CHECK_GPU(x);
+  check_nhwc(x, "x");
+  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  TORCH_CHECK(scale.numel() == C && shift.numel() == C &&
+                  scale.scalar_type() == at::kFloat &&
+                  shift.scalar_type() == at::kFloat,
+              "bn_act_maxpool_fwd: scale/shift are fp32 [C]");
+  TORCH_CHECK(act == 0 || act == 1, "bn_act_maxpool_fwd: act none or relu");
+  TORCH_CHECK((int64_t)N * Ho <= 65535,
+              "bn_act_maxpool_fwd: N * Ho exceeds the grid limit");
+  auto y = at::empty({N, C, Ho, Wo},
+                     x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  auto idx = at::empty({N, C, Ho, Wo},
+                       x.options()
+                           .dtype(at::kByte)
+                           .memory_format(at::MemoryFormat::ChannelsLast));
+  DISPATCH_FLOAT_AND_BF16(x.scalar_type(), "bn_act_maxpool_fwd", [&] {
+    constexpr int V = 16 / sizeof(scalar_t);
+    TORCH_CHECK(C % V == 0, "C must be divisible by ", V);
+    const int cpacks = C / V;
+    const int64_t rowpacks = (int64_t)Wo * cpacks;
+    TORCH_CHECK(rowpacks * cpacks < (1LL << 47) && rowpacks < (1LL << 31) &&
+                    (int64_t)W * cpacks < (1LL << 30),
+                "bn_act_maxpool_fwd: row too wide");
+    launch_bn_act_maxpool_fwd<scalar_t>(x, scale, shift, y, idx, N, H, W, C,
+                                        Ho, Wo, (int)act, cur_stream());
+  });
+  return {y, idx};
+}
+
+// Local raw grad-stat sums [2C] of the BN under a (3, 2, 1) maxpool, from the
+// POOLED gradient (the bn_bwd_stats counterpart; SyncBN all-reduces these).
+at::Tensor bn_pool_bwd_stats(at::Tensor gpool, at::Tensor idx, at::Tensor x,
+                             at::Tensor scale, at::Tensor shift,
+                             int64_t act) {
+  auto hw = check_pool_bwd_args(gpool, idx, x);
+  const int C = x.size(1), H = x.size(2), W = x.size(3);
+  const int64_t rows = x.numel() / C;
+  auto fopts = x.options().dtype(at::kFloat);
+  at::Tensor both;
+  DISPATCH_FLOAT_AND_BF16(x.scalar_type(), "bn_pool_bwd_stats", [&] {
+    constexpr int V = 16 / sizeof(scalar_t);
+    TORCH_CHECK(C % V == 0, "C must be divisible by ", V);
+    auto stream = cur_stream();
+    const int cpacks = C / V;
+    const int nrl = std::max(256 / cpacks, 1);
+    const int64_t rpb = pick_rows_per_block(rows, nrl);
+    const int rgrid = (int)ceil_div(rows, rpb);
+    auto part = at::empty({rgrid, 2 * C}, fopts);
+    launch_pool_bwd_reduce<scalar_t>(gpool, idx, x, scale, shift, part, rows,
+                                     C, H, W, hw.first, hw.second, rpb,
+                                     (int)act, rgrid, stream);
+    both = at::empty({2 * C}, fopts);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((int)ceil_div(2 * C, 64)),
+                       dim3(256), 0, stream, part.data_ptr<float>(),
+                       both.data_ptr<float>(), 2 * C, rgrid);
+  });
+  return both;
+}
+
+// dx/gw/gb given (possibly cross-rank-reduced) raw sums and the TOTAL count.
+std::vector<at::Tensor> bn_pool_bwd_apply(at::Tensor gpool, at::Tensor idx,
+                                          at::Tensor x, at::Tensor mean,
+                                          at::Tensor rstd, at::Tensor gamma,
+                                          at::Tensor scale, at::Tensor shift,
+                                          at::Tensor sums, double total_count,
+                                          int64_t act, bool training) {
+  auto hw = check_pool_bwd_args(gpool, idx, x);
+  const int C = x.size(1), H = x.size(2), W = x.size(3);
+  const int64_t rows = x.numel() / C;
+  auto fopts = x.options().dtype(at::kFloat);
+  auto gx = at::empty_like(x);
+  auto gw = at::empty({C}, fopts);
+  auto gb = at::empty({C}, fopts);
+  auto P1 = at::empty({C}, fopts);
+  auto P2 = at::empty({C}, fopts);
+  auto P3 = at::empty({C}, fopts);
+  DISPATCH_FLOAT_AND_BF16(x.scalar_type(), "bn_pool_bwd_apply", [&] {
+    constexpr int V = 16 / sizeof(scalar_t);
+    TORCH_CHECK(C % V == 0, "C must be divisible by ", V);
+    auto stream = cur_stream();
+    const float inv_cnt = 1.f / (float)total_count;
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((int)ceil_div(C, 16)),
+                       dim3(256), 0, stream, sums.data_ptr<float>(), 1,
+                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                       gamma.data_ptr<float>(), gw.data_ptr<float>(),
+                       gb.data_ptr<float>(), P1.data_ptr<float>(),
+                       P2.data_ptr<float>(), P3.data_ptr<float>(), C, inv_cnt,
+                       training ? 1 : 0);
+    const int cpacks = C / V;
+    const int nrl = std::max(256 / cpacks, 1);
+    const int64_t rpb = pick_rows_per_block(rows, nrl);
+    const int rgrid = (int)ceil_div(rows, rpb);
+    launch_pool_bwd_dx<scalar_t>(gpool, idx, x, scale, shift, P1, P2, P3, gx,
+                                 rows, C, H, W, hw.first, hw.second, rpb,
+                                 (int)act, rgrid, stream);
+  });
+  return {gx, gw, gb};
+}
+
+// Full backward of BN(+act) -> maxpool(3, 2, 1): reduce -> finalize -> dx.
+std::vector<at::Tensor> bn_pool_bwd(at::Tensor gpool, at::Tensor idx,
+                                    at::Tensor x, at::Tensor mean,
+                                    at::Tensor rstd, at::Tensor gamma,
+                                    at::Tensor scale, at::Tensor shift,
+                                    int64_t act, bool training) {
+  auto hw = check_pool_bwd_args(gpool, idx, x);
+  const int C = x.size(1), H = x.size(2), W = x.size(3);
+  const int64_t rows = x.numel() / C;
+  auto fopts = x.options().dtype(at::kFloat);
+  auto gx = at::empty_like(x);
+  auto gw = at::empty({C}, fopts);
+  auto gb = at::empty({C}, fopts);
+  auto P1 = at::empty({C}, fopts);
+  auto P2 = at::empty({C}, fopts);
+  auto P3 = at::empty({C}, fopts);
+  DISPATCH_FLOAT_AND_BF16(x.scalar_type(), "bn_pool_bwd", [&] {
+    constexpr int V = 16 / sizeof(scalar_t);
+    TORCH_CHECK(C % V == 0, "C must be divisible by ", V);
+    auto stream = cur_stream();
+    const int cpacks = C / V;
+    const int nrl = std::max(256 / cpacks, 1);
+    const int64_t rpb = pick_rows_per_block(rows, nrl);
+    const int rgrid = (int)ceil_div(rows, rpb);
+    auto part = at::empty({rgrid, 2 * C}, fopts);
+    launch_pool_bwd_reduce<scalar_t>(gpool, idx, x, scale, shift, part, rows,
+                                     C, H, W, hw.first, hw.second, rpb,
+                                     (int)act, rgrid, stream);
+    const float inv_cnt = 1.f / (float)rows;
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((int)ceil_div(C, 16)),
+                       dim3(256), 0, stream, part.data_ptr<float>(), rgrid,
+                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                       gamma.data_ptr<float>(), gw.data_ptr<float>(),
+                       gb.data_ptr<float>(), P1.data_ptr<float>(),
+                       P2.data_ptr<float>(), P3.data_ptr<float>(), C, inv_cnt,
+                       training ? 1 : 0);
+    launch_pool_bwd_dx<scalar_t>(gpool, idx, x, scale, shift, P1, P2, P3, gx,
+                                 rows, C, H, W, hw.first, hw.second, rpb,
+                                 (int)act, rgrid, stream);
+  });
+  return {gx, gw, gb};
 }

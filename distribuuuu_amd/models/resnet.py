@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from ..ops import functional as DF
 from ..ops import AdaptiveAvgPool2d, BatchNorm2d, Conv2d, Linear, MaxPool2d
+from ..ops.modules import shortcut
 
 
 def conv3x3(cin, cout, stride=1, groups=1, dilation=1):
@@ -42,10 +43,13 @@ class BasicBlock(nn.Module):
 
     def forward(self, x):
         xm, xs = DF.fork(x)
-        identity = xs if self.downsample is None else self.downsample(xs)
+        # downsample blocks hand bn2 the raw shortcut conv + its BN module
+        identity, id_bn = shortcut(self.downsample, xs, self.bn2)
         out = self.bn1(self.conv1(xm))
         out = self.conv2(out)
-        return self.bn2(out, residual=identity)
+        if id_bn is None:
+            return self.bn2(out, residual=identity)
+        return self.bn2(out, residual=identity, residual_bn=id_bn)
 
 
 class Bottleneck(nn.Module):
@@ -67,11 +71,14 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         xm, xs = DF.fork(x)
-        identity = xs if self.downsample is None else self.downsample(xs)
+        # downsample blocks hand bn3 the raw shortcut conv + its BN module
+        identity, id_bn = shortcut(self.downsample, xs, self.bn3)
         out = self.bn1(self.conv1(xm))
         out = self.bn2(self.conv2(out))
         out = self.conv3(out)
-        return self.bn3(out, residual=identity)
+        if id_bn is None:
+            return self.bn3(out, residual=identity)
+        return self.bn3(out, residual=identity, residual_bn=id_bn)
 
 
 class ResNet(nn.Module):
@@ -120,7 +127,8 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.maxpool(self.bn1(self.conv1(x)))
+        # bn1 + relu + maxpool as one op (both modules stay for state_dict)
+        x = self.bn1.forward_maxpool(self.conv1(x), self.maxpool)
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = self.avgpool(x)
         return self.fc(x.flatten(1))

@@ -458,31 +458,42 @@ class _HIPBatchNormAct(torch.autograd.Function):
                 None, None)
 
 
+def _bn_stats_half(x, weight, bias, running_mean, running_var, training,
+                   momentum, eps):
+    """Stats half of a HIP BatchNorm: conv-epilogue partials (F1) when the
+    producing conv emitted them, running-stat update, and the fused
+    scale/shift coefficients. Returns (x_cl, mean, rstd, scale, shift)."""
+    part = getattr(x, "_bn_partials", None) if training else None
+    if training and part is None:
+        srcw = getattr(x, "_bn_src_weight", None)
+        if srcw is not None:
+            # flag the producing conv: it emits partials from now on
+            srcw._emit_bn_partials = True
+    e = ext()
+    x = _cl(x)
+    rm, rv = running_mean, running_var
+    with torch.no_grad():
+        gamma = weight.float().contiguous()
+        beta = bias.float().contiguous()
+        copy_back = False
+        if rm is not None and rm.dtype != torch.float32:
+            rm, rv = rm.float(), rv.float()
+            copy_back = True
+        mean, rstd, scale, shift = e.bn_stats(
+            x, gamma, beta, rm, rv, momentum, eps, training, part)
+        if copy_back:
+            running_mean.copy_(rm)
+            running_var.copy_(rv)
+    return x, mean, rstd, scale, shift
+
+
 def batch_norm_act(x, weight, bias, running_mean, running_var, training=False,
                    momentum=0.1, eps=1e-5, act="none", residual=None):
     if use_hip(x, "bn_sums"):
-        part = getattr(x, "_bn_partials", None) if training else None
-        if training and part is None:
-            srcw = getattr(x, "_bn_src_weight", None)
-            if srcw is not None:
-                # flag the producing conv: it emits partials from now on
-                srcw._emit_bn_partials = True
-        e = ext()
         act_id = _ACTS[act]
-        x = _cl(x)
-        rm, rv = running_mean, running_var
-        with torch.no_grad():
-            gamma = weight.float().contiguous()
-            beta = bias.float().contiguous()
-            copy_back = False
-            if rm is not None and rm.dtype != torch.float32:
-                rm, rv = rm.float(), rv.float()
-                copy_back = True
-            mean, rstd, scale, shift = e.bn_stats(
-                x, gamma, beta, rm, rv, momentum, eps, training, part)
-            if copy_back:
-                running_mean.copy_(rm)
-                running_var.copy_(rv)
+        x, mean, rstd, scale, shift = _bn_stats_half(
+            x, weight, bias, running_mean, running_var, training, momentum,
+            eps)
         # dgrad-side backward-stat emission is measured NET-NEGATIVE on
         # ResNet-50 (the EMODE-2 epilogue's extra x stream + barrier
         # serialization costs ~1.6 ms/step while removing only ~0.8 ms of
@@ -531,6 +542,122 @@ def batch_norm_act(x, weight, bias, running_mean, running_var, training=False,
     if residual is not None:
         y = y + residual
     return _apply_act(y, act)
+
+
+def _bn_fuse_on(part):
+    # DISTRIBUUUU_BN_FUSE: unset/1 = both fused paths, 0 = neither (the tests
+    # compare both ways bit for bit), "stem" / "shortcut" = that one alone
+    # (A/B measurements)
+    v = os.environ.get("DISTRIBUUUU_BN_FUSE", "1")
+    return v == part or v not in ("0", "stem", "shortcut")
+
+
+def _pack_ok(x):
+    """dtype/channel gate of the packed BN kernels (16-byte channel packs)."""
+    if x.dtype == torch.bfloat16:
+        return x.shape[1] % 8 == 0
+    return x.dtype == torch.float32 and x.shape[1] % 4 == 0
+
+
+class _HIPBatchNormActMaxPool(torch.autograd.Function):
+    """BN(+relu) -> maxpool(3, 2, 1) of the stem as one forward kernel and a
+    reduce/dx backward pair that gathers g from the pooled gradient: neither
+    the full-size BN output nor the full-size pooled-gradient tensor exists.
+    Bit-identical to batch_norm_act -> max_pool2d."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mean, rstd, scale, shift, training,
+                act_id):
+        y, idx = ext().bn_act_maxpool_fwd(x, scale, shift, act_id)
+        ctx.save_for_backward(x, weight, scale, shift, mean, rstd, idx)
+        ctx.act_id = act_id
+        ctx.training = training
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, scale, shift, mean, rstd, idx = ctx.saved_tensors
+        gamma = weight.float().contiguous()
+        gx, gw, gb = ext().bn_pool_bwd(_cl(gy), idx, x, mean, rstd, gamma,
+                                       scale, shift, ctx.act_id, ctx.training)
+        return (gx, gw.to(weight.dtype), gb.to(weight.dtype), None, None,
+                None, None, None, None)
+
+
+def batch_norm_act_maxpool(x, weight, bias, running_mean, running_var,
+                           training=False, momentum=0.1, eps=1e-5, act="none",
+                           kernel_size=3, stride=2, padding=1):
+    """max_pool2d(batch_norm_act(x, ...)) — fused on the HIP path for the
+    (3, 2, 1) pool with act none/relu, today's two calls everywhere else."""
+    if (x.is_cuda and x.dim() == 4 and act in ("none", "relu")
+            and (kernel_size, stride, padding) == (3, 2, 1) and _pack_ok(x)
+            # one grid row per pooled output row
+            and x.shape[0] * ((x.shape[2] - 1) // 2 + 1) <= 65535
+            and _bn_fuse_on("stem") and use_hip(x, "bn_act_maxpool_fwd")):
+        x, mean, rstd, scale, shift = _bn_stats_half(
+            x, weight, bias, running_mean, running_var, training, momentum,
+            eps)
+        return _HIPBatchNormActMaxPool.apply(x, weight, bias, mean, rstd,
+                                             scale, shift, training,
+                                             _ACTS[act])
+    y = batch_norm_act(x, weight, bias, running_mean, running_var, training,
+                       momentum, eps, act)
+    return max_pool2d(y, kernel_size, stride, padding)
+
+
+class _HIPBatchNormActDual(torch.autograd.Function):
+    """Residual-join BN of a downsample block with the shortcut BN applied in
+    the same pass: y = relu(bn(x) + bn_s(xr)), xr the RAW shortcut-conv
+    output. The identity tensor is never materialised. Backward is today's
+    chain on the same values: masked bn_bwd for the join BN, then
+    bn_bwd(act none) for the shortcut BN on the resulting gres."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, xr, rweight, rbias, mean, rstd, scale,
+                shift, rmean, rrstd, rscale, rshift):
+        y, mask = ext().bn_apply_act_mask(x, scale, shift, 1, xr, rscale,
+                                          rshift)
+        ctx.save_for_backward(x, weight, scale, shift, mean, rstd, xr,
+                              rweight, rscale, rshift, rmean, rrstd, mask)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x, weight, scale, shift, mean, rstd, xr, rweight, rscale, rshift,
+         rmean, rrstd, mask) = ctx.saved_tensors
+        e = ext()
+        # the masked kernels never read the residual stream; xr only fills
+        # the pointer slot
+        gx, gw, gb, gres = e.bn_bwd(
+            _cl(gy), x, xr, mean, rstd, weight.float().contiguous(), scale,
+            shift, 1, True, True, mask=mask)
+        gxr, grw, grb, _ = e.bn_bwd(
+            gres, xr, None, rmean, rrstd, rweight.float().contiguous(),
+            rscale, rshift, 0, True, False, mask=None)
+        return (gx, gw.to(weight.dtype), gb.to(weight.dtype), gxr,
+                grw.to(rweight.dtype), grb.to(rweight.dtype), None, None,
+                None, None, None, None, None, None)
+
+
+def dual_bn_ok(x):
+    """Whether the join BN of a downsample block can apply the shortcut BN
+    itself: exactly the conditions of the relu bitmask path (training-mode
+    module checks are the caller's)."""
+    return (x.is_cuda and torch.is_grad_enabled() and _pack_ok(x)
+            and os.environ.get("DISTRIBUUUU_BN_MASK", "1") != "0"
+            and _bn_fuse_on("shortcut")
+            and use_hip(x, "bn_apply_act_mask"))
+
+
+def batch_norm_act_dual(x, bn, xr, rbn):
+    """relu(bn(x) + rbn(xr)) for two training-mode (weight, bias,
+    running_mean, running_var, momentum, eps) parameter tuples."""
+    xr, rmean, rrstd, rscale, rshift = _bn_stats_half(xr, *rbn[:4], True,
+                                                      *rbn[4:])
+    x, mean, rstd, scale, shift = _bn_stats_half(x, *bn[:4], True, *bn[4:])
+    return _HIPBatchNormActDual.apply(x, bn[0], bn[1], xr, rbn[0], rbn[1],
+                                      mean, rstd, scale, shift, rmean, rrstd,
+                                      rscale, rshift)
 
 
 class _Fork(torch.autograd.Function):

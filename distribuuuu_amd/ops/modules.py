@@ -86,16 +86,65 @@ class BatchNorm2d(nn.Module):
             self.num_batches_tracked += self._nbt_pending
             self._nbt_pending = 0
 
-    def forward(self, x, residual=None):
+    def forward(self, x, residual=None, residual_bn=None):
         if self.training:
             self._nbt_pending += 1
+        if residual_bn is not None:
+            # downsample block: ``residual`` is the raw shortcut-conv output
+            # and its BN is applied inside this BN's apply kernel; shortcut()
+            # below is the gate (both BNs plain, training, relu mask path)
+            assert self.training and residual_bn.training and \
+                self.act == "relu", "residual_bn needs the relu mask path"
+            residual_bn._nbt_pending += 1
+            return DF.batch_norm_act_dual(x, self._bn_args(), residual,
+                                          residual_bn._bn_args())
         return DF.batch_norm_act(
             x, self.weight, self.bias, self.running_mean, self.running_var,
             self.training, self.momentum, self.eps, self.act, residual,
         )
 
+    def _bn_args(self):
+        return (self.weight, self.bias, self.running_mean, self.running_var,
+                self.momentum, self.eps)
+
+    def forward_maxpool(self, x, pool):
+        """pool(self(x)); the plain BN + MaxPool2d(3, 2, 1) pair of a stem
+        runs as one fused op on the HIP path (DF.batch_norm_act_maxpool)."""
+        if type(self) is not BatchNorm2d or type(pool) is not MaxPool2d:
+            return pool(self(x))
+        if self.training:
+            self._nbt_pending += 1
+        return DF.batch_norm_act_maxpool(
+            x, self.weight, self.bias, self.running_mean, self.running_var,
+            self.training, self.momentum, self.eps, self.act,
+            pool.kernel_size, pool.stride, pool.padding,
+        )
+
     def extra_repr(self):
         return f"{self.num_features}, eps={self.eps}, act={self.act}"
+
+
+def shortcut(downsample, xs, join_bn):
+    """Shortcut branch of a residual block -> (residual, residual_bn) for
+    ``join_bn(out, residual=..., residual_bn=...)``.
+
+    A conv -> plain-BN downsample whose join BN takes the relu bitmask path
+    returns the RAW conv output and the shortcut BN module: the join BN's
+    apply kernel normalises it in the same pass and the identity tensor is
+    never written. Every other case returns (identity, None) as before."""
+    if downsample is None:
+        return xs, None
+    if (isinstance(downsample, nn.Sequential) and len(downsample) == 2
+            and type(downsample[0]) is Conv2d
+            and type(downsample[1]) is BatchNorm2d
+            and type(join_bn) is BatchNorm2d
+            and join_bn.act == "relu" and downsample[1].act == "none"
+            and join_bn.training and downsample[1].training):
+        xr = downsample[0](xs)
+        if DF.dual_bn_ok(xr):
+            return xr, downsample[1]
+        return downsample[1](xr), None
+    return downsample(xs), None
 
 
 class ReLU(nn.Module):

@@ -1,7 +1,7 @@
 """Per-kernel micro-benchmarks on representative ResNet-50 shapes.
 
 Usage (on a GPU box): python tools/kbench.py [--deterministic] [group ...]
-Groups: bn conv wgrad pool gemm sgd all
+Groups: bn conv wgrad pool fused gemm sgd all
 Prints achieved GB/s (memory-bound ops) or TF/s (MFMA ops) per shape.
 --deterministic: the wgrad rows time each shape in both modes, atomic and
 deterministic (docs/DETERMINISM.md), side by side.
@@ -143,6 +143,57 @@ def bench_pool():
     print(f"gap_fwd      {t*1e6:8.1f} us  {x2.numel()*2/t/1e9:7.0f} GB/s")
 
 
+def bench_fused():
+    """Fused stem BN+ReLU+maxpool and the dual (join + shortcut BN) apply,
+    each next to the kernels it replaces. GB/s counts the fused op's own
+    compulsory bytes (gathers of the pooled gradient counted once per
+    kernel)."""
+    print("== fused bn ops vs the chains they replace ==")
+    shp = (256, 64, 112, 112)
+    c = shp[1]
+    x = _cl(torch.randn(*shp, device=DEV, dtype=torch.bfloat16))
+    nb = x.numel() * 2
+    g = torch.rand(c, device=DEV) + 0.5
+    b = torch.zeros(c, device=DEV)
+    mean, rstd, sc, sh = e.bn_stats(x, g, b, None, None, 0.1, 1e-5, True, None)
+    t_ap = timeit(lambda: e.bn_apply_act(x, sc, sh, 1, None))
+    y = e.bn_apply_act(x, sc, sh, 1, None)
+    t_mp = timeit(lambda: e.maxpool_fwd(y, 3, 2, 1))
+    t_f = timeit(lambda: e.bn_act_maxpool_fwd(x, sc, sh, 1))
+    fb = nb + nb // 4 + nb // 8
+    print(f"stem fwd  bn_apply {t_ap*1e6:7.1f} + maxpool_fwd {t_mp*1e6:7.1f} "
+          f"= {(t_ap+t_mp)*1e6:7.1f} us | fused {t_f*1e6:7.1f} us "
+          f"{fb/t_f/1e9:6.0f} GB/s")
+    yp, idx = e.bn_act_maxpool_fwd(x, sc, sh, 1)
+    del y
+    gp = _cl(torch.randn_like(yp))
+    t_mb = timeit(lambda: e.maxpool_bwd(gp, idx, shp[2], shp[3], 3, 2, 1))
+    gfull = e.maxpool_bwd(gp, idx, shp[2], shp[3], 3, 2, 1)
+    t_bb = timeit(lambda: e.bn_bwd(gfull, x, None, mean, rstd, g, sc, sh, 1,
+                                   True, False))
+    del gfull
+    t_fb = timeit(lambda: e.bn_pool_bwd(gp, idx, x, mean, rstd, g, sc, sh, 1,
+                                        True))
+    bb = 3 * nb + 2 * (nb // 4 + nb // 8)
+    print(f"stem bwd  maxpool_bwd {t_mb*1e6:7.1f} + bn_bwd {t_bb*1e6:7.1f} "
+          f"= {(t_mb+t_bb)*1e6:7.1f} us | fused {t_fb*1e6:7.1f} us "
+          f"{bb/t_fb/1e9:6.0f} GB/s")
+    shp = (256, 256, 56, 56)
+    c = shp[1]
+    x = _cl(torch.randn(*shp, device=DEV, dtype=torch.bfloat16))
+    xr = _cl(torch.randn_like(x))
+    nb = x.numel() * 2
+    sc, sh, rsc, rsh = (torch.randn(c, device=DEV) for _ in range(4))
+    t_id = timeit(lambda: e.bn_apply_act(xr, rsc, rsh, 0, None))
+    ident = e.bn_apply_act(xr, rsc, rsh, 0, None)
+    t_jn = timeit(lambda: e.bn_apply_act_mask(x, sc, sh, 1, ident))
+    t_du = timeit(lambda: e.bn_apply_act_mask(x, sc, sh, 1, xr, rsc, rsh))
+    db = 3 * nb + nb // 16
+    print(f"dual apply {str(shp):20s} shortcut apply {t_id*1e6:7.1f} + join "
+          f"{t_jn*1e6:7.1f} = {(t_id+t_jn)*1e6:7.1f} us | fused "
+          f"{t_du*1e6:7.1f} us {db/t_du/1e9:6.0f} GB/s")
+
+
 def bench_gemm():
     print("== gemm_nt (TF/s) ==")
     for m, n, k in [(256, 1000, 2048), (4096, 4096, 4096), (8192, 8192, 8192)]:
@@ -215,6 +266,8 @@ if __name__ == "__main__":
         bench_wgrad(deterministic)
     if "pool" in groups or "all" in groups:
         bench_pool()
+    if "fused" in groups or "all" in groups:
+        bench_fused()
     if "gemm" in groups or "all" in groups:
         bench_gemm()
     if "sgd" in groups or "all" in groups:
