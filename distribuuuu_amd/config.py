@@ -186,6 +186,13 @@ _C.TRAIN.DTYPE = "float32"          # "float32" | "bfloat16" (bf16 compute, fp32
 _C.TRAIN.CHANNELS_LAST = False       # NHWC end-to-end
 _C.TRAIN.BUCKET_CAP_MB = 8           # DDP gradient bucket size, tuned for 7-link xGMI
 _C.TRAIN.COMPILE_GRAPH = False       # capture the train step in a hipGraph
+# soft-target training (mixing.SoftTargetCriterion); all at default = the
+# plain hard-target loss and no batch mixing
+_C.TRAIN.LABEL_SMOOTH = 0.0          # label smoothing eps in [0, 1)
+_C.TRAIN.MIXUP_ALPHA = 0.0           # mixup: lam ~ Beta(alpha, alpha); 0 = off
+_C.TRAIN.CUTMIX_ALPHA = 0.0          # CutMix box from Beta(alpha, alpha); 0 = off
+_C.TRAIN.MIX_PROB = 1.0              # probability that a batch is mixed at all
+_C.TRAIN.MIX_SWITCH_PROB = 0.5       # CutMix (vs mixup) when both alphas are set
 
 _C.TEST = CfgNode()
 _C.TEST.DATASET = "./data/ILSVRC/"

@@ -79,8 +79,17 @@ at::Tensor avgpool_bwd(at::Tensor gy, int64_t K, int64_t S, int64_t H,
 std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target);
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
                   at::Tensor gl);
+std::vector<at::Tensor> ce_soft_fwd(at::Tensor logits, at::Tensor target,
+                                    c10::optional<at::Tensor> lam,
+                                    double eps);
+at::Tensor ce_soft_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
+                       at::Tensor gl, c10::optional<at::Tensor> lam,
+                       double eps);
 std::vector<at::Tensor> topk_acc(at::Tensor logits, at::Tensor target,
                                  int64_t topk);
+// mix.hip
+at::Tensor batch_mix(at::Tensor x, int64_t mode, double lam, int64_t y0,
+                     int64_t y1, int64_t x0, int64_t x1);
 // conv.hip
 at::Tensor conv2d_fwd_v1(at::Tensor x, at::Tensor w, at::Tensor y,
                          int64_t Ho, int64_t Wo, int64_t sh, int64_t sw,
@@ -217,6 +226,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("avgpool_bwd", &avgpool_bwd);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);
+  m.def("ce_soft_fwd", &ce_soft_fwd, py::arg("logits"), py::arg("target"),
+        py::arg("lam") = py::none(), py::arg("eps") = 0.0);
+  m.def("ce_soft_bwd", &ce_soft_bwd, py::arg("logits"), py::arg("target"),
+        py::arg("lse"), py::arg("gl"), py::arg("lam") = py::none(),
+        py::arg("eps") = 0.0);
+  m.def("batch_mix", &batch_mix, py::arg("x"), py::arg("mode"),
+        py::arg("lam"), py::arg("y0"), py::arg("y1"), py::arg("x0"),
+        py::arg("x1"));
   m.def("topk_acc", &topk_acc);
   m.def("sgd_step", &sgd_step);
   m.def("sgd_step_dev", &sgd_step_dev);

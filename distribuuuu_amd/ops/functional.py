@@ -909,10 +909,103 @@ class _HIPCrossEntropy(torch.autograd.Function):
         return gx, None
 
 
-def cross_entropy(logits, target):
-    if use_hip(logits, "ce_fwd"):
-        return _HIPCrossEntropy.apply(logits, target)
-    return F.cross_entropy(logits, target)
+class _HIPSoftCrossEntropy(torch.autograd.Function):
+    """Cross-entropy on smoothed, batch-mixed targets (soft_targets below).
+    `lam` is a float32 device tensor of one element that both kernels read
+    from memory, never a launch argument: a hipGraph replay follows the value
+    filled in before it. None means lam = 1."""
+
+    @staticmethod
+    def forward(ctx, logits, target, lam, eps):
+        logits = logits.contiguous()
+        loss, lse = ext().ce_soft_fwd(logits, target, lam, eps)
+        ctx.save_for_backward(logits, target, lse)
+        ctx.lam = lam
+        ctx.eps = eps
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        logits, target, lse = ctx.saved_tensors
+        gx = ext().ce_soft_bwd(logits, target, lse, gl.contiguous(), ctx.lam,
+                               ctx.eps)
+        return gx, None, None, None
+
+
+def soft_targets(target, num_classes, label_smoothing=0.0, lam=None,
+                 dtype=torch.float32):
+    """q[n, j] = (1-eps) * (lam*[j==a] + (1-lam)*[j==b]) + eps/K with
+    a = target[n] and b = target[N-1-n]: sample n is paired with sample
+    N-1-n (the batch against its own reversal), lam weighs its own label."""
+    q = F.one_hot(target, num_classes).to(dtype)
+    if lam is not None:
+        lam = lam.to(device=q.device, dtype=dtype).reshape(())
+        q = lam * q + (1 - lam) * q.flip(0)
+    return (1.0 - label_smoothing) * q + label_smoothing / num_classes
+
+
+def cross_entropy(logits, target, label_smoothing=0.0, lam=None):
+    """Mean cross-entropy. `label_smoothing` (host float in [0, 1)) and `lam`
+    (one-element float32 tensor, the weight of each sample's own label
+    against its batch-reversal partner's) select the soft-target loss; with
+    both at their defaults this is the hard-target loss and kernels."""
+    if label_smoothing == 0.0 and lam is None:
+        if use_hip(logits, "ce_fwd"):
+            return _HIPCrossEntropy.apply(logits, target)
+        return F.cross_entropy(logits, target)
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got "
+                         f"{label_smoothing}")
+    if use_hip(logits, "ce_soft_fwd"):
+        return _HIPSoftCrossEntropy.apply(logits, target, lam,
+                                          float(label_smoothing))
+    q = soft_targets(target, logits.shape[1], label_smoothing, lam,
+                     logits.dtype)
+    return F.cross_entropy(logits, q)
+
+
+# ---------------------------------------------------------------------------
+# Batch mixing (mixup / CutMix) against the reversed batch
+# ---------------------------------------------------------------------------
+def batch_mix(x, lam, box=None):
+    """Mix every sample of x [N, C, H, W] with its partner x[N-1-n], out of
+    place. box None: mixup, lam * x + (1 - lam) * partner in fp32, rounded
+    once to x's dtype (lam 1 and 0 return x and x.flip(0) to the bit).
+    box (y0, y1, x0, x1): CutMix, the partner's pixels inside
+    [y0, y1) x [x0, x1) and x's own outside; lam is not used."""
+    if x.dim() != 4:
+        raise ValueError("batch_mix expects [N, C, H, W]")
+    if not (x.is_contiguous()
+            or x.is_contiguous(memory_format=torch.channels_last)):
+        # dense in its own memory format
+        nhwc = x.shape[1] > 1 and x.stride(1) == 1
+        x = x.contiguous(memory_format=torch.channels_last if nhwc
+                         else torch.contiguous_format)
+    if box is not None:
+        y0, y1, x0, x1 = (int(v) for v in box)
+        h, w = x.shape[2], x.shape[3]
+        if not (0 <= y0 <= y1 <= h and 0 <= x0 <= x1 <= w):
+            raise ValueError(f"box {box} outside the {h}x{w} image")
+    elif not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lam must be in [0, 1], got {lam}")
+    if (x.dtype in (torch.float32, torch.bfloat16)
+            and use_hip(x, "batch_mix")):
+        if box is None:
+            return ext().batch_mix(x, 0, float(lam), 0, 0, 0, 0)
+        return ext().batch_mix(x, 1, 1.0, y0, y1, x0, x1)
+    if x.is_cuda and x.dtype not in (torch.float32, torch.bfloat16):
+        fallback_warn("batch_mix", f"dtype {x.dtype} (fp32/bf16 kernels)")
+    if box is not None:
+        inside = torch.zeros(1, 1, x.shape[2], x.shape[3], dtype=torch.bool,
+                             device=x.device)
+        inside[:, :, y0:y1, x0:x1] = True
+        return torch.where(inside, x.flip(0), x)
+    lam32 = torch.tensor(lam, dtype=torch.float32)
+    if lam32 == 1:
+        return x.clone()
+    if lam32 == 0:
+        return x.flip(0)
+    return (lam32 * x.float() + (1 - lam32) * x.flip(0).float()).to(x.dtype)
 
 
 # ---------------------------------------------------------------------------

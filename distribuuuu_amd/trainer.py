@@ -22,6 +22,7 @@ from .config import cfg
 from .data import construct_train_loader, construct_val_loader
 from .graph_step import GraphedTrainStep
 from .logger import logger, setup_logger
+from .mixing import SoftTargetCriterion
 from .ops import functional as DF
 from .parallel import DistributedDataParallel, convert_sync_batchnorm
 from . import utils
@@ -57,6 +58,20 @@ def build_network(device):
     if cfg.TRAIN.CHANNELS_LAST:
         net = net.to(memory_format=torch.channels_last)
     return net
+
+
+def build_criterion(rank=0):
+    """The training loss: DF.cross_entropy itself unless a soft-target key
+    (TRAIN.LABEL_SMOOTH / MIXUP_ALPHA / CUTMIX_ALPHA) is set, then one
+    mixing.SoftTargetCriterion drawing from RNG_SEED + rank when seeded."""
+    if (cfg.TRAIN.LABEL_SMOOTH == 0.0 and cfg.TRAIN.MIXUP_ALPHA == 0.0
+            and cfg.TRAIN.CUTMIX_ALPHA == 0.0):
+        return DF.cross_entropy
+    seed = None if cfg.RNG_SEED is None else int(cfg.RNG_SEED) + rank
+    return SoftTargetCriterion(
+        cfg.TRAIN.LABEL_SMOOTH, cfg.TRAIN.MIXUP_ALPHA, cfg.TRAIN.CUTMIX_ALPHA,
+        prob=cfg.TRAIN.MIX_PROB, switch_prob=cfg.TRAIN.MIX_SWITCH_PROB,
+        seed=seed)
 
 
 def _own_runner(net, criterion, optimizer, topk, device, dtype):
@@ -100,6 +115,12 @@ def train_epoch(train_loader, net, criterion, optimizer, epoch, device, dtype,
     if hasattr(train_loader, "sampler") and hasattr(train_loader.sampler,
                                                     "set_epoch"):
         train_loader.sampler.set_epoch(epoch)
+    # a soft-target criterion (mixing.SoftTargetCriterion) mixes the prepared
+    # batch before the step, eager or captured: the runner's input copy is
+    # then device-to-device in one dtype, so both see the same bits
+    mix = getattr(criterion, "mix", None)
+    if mix is not None:
+        criterion.set_epoch(epoch)
     net.train()
     # world==1: set_to_none skips the per-step grad memsets (161 for ResNet-50);
     # under DDP the bucket grad-views must stay installed, so keep memsets there
@@ -107,10 +128,15 @@ def train_epoch(train_loader, net, criterion, optimizer, epoch, device, dtype,
     end = time.time()
     for idx, (inputs, targets) in enumerate(train_loader):
         data_time.update(time.time() - end)
+        if mix is not None:
+            inputs, targets = _prepare_batch(inputs, targets, device, dtype)
+            inputs = mix(inputs)
         if graph_step is not None:
             loss, acc1, acck = graph_step(inputs, targets)
         else:
-            inputs, targets = _prepare_batch(inputs, targets, device, dtype)
+            if mix is None:
+                inputs, targets = _prepare_batch(inputs, targets, device,
+                                                 dtype)
             outputs = net(inputs)
             loss = criterion(outputs.float(), targets)
             optimizer.zero_grad(set_to_none=zero_none)
@@ -172,7 +198,7 @@ def train_model():
         net = DistributedDataParallel(net, bucket_cap_mb=cfg.TRAIN.BUCKET_CAP_MB)
     train_loader = construct_train_loader()
     val_loader = construct_val_loader()
-    criterion = DF.cross_entropy
+    criterion = build_criterion(rank)  # validation stays on the plain loss
     optimizer = utils.construct_optimizer(net)
 
     n_params, mb = utils.count_parameters(net)
@@ -206,7 +232,8 @@ def train_model():
     for epoch in range(start_epoch, cfg.OPTIM.MAX_EPOCH):
         train_epoch(train_loader, net, criterion, optimizer, epoch, device,
                     dtype, graph_step=graph_step)
-        acc1, acck = validate(val_loader, net, criterion, device, dtype)
+        acc1, acck = validate(val_loader, net, DF.cross_entropy, device,
+                              dtype)
         best = acc1 > best_acc1
         best_acc1 = max(acc1, best_acc1)
         path = utils.save_checkpoint(net, optimizer, epoch, best_acc1, best)

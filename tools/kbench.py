@@ -1,7 +1,7 @@
 """Per-kernel micro-benchmarks on representative ResNet-50 shapes.
 
 Usage (on a GPU box): python tools/kbench.py [--deterministic] [group ...]
-Groups: bn conv wgrad pool fused gemm sgd all
+Groups: bn conv wgrad pool fused gemm sgd mix all
 Prints achieved GB/s (memory-bound ops) or TF/s (MFMA ops) per shape.
 --deterministic: the wgrad rows time each shape in both modes, atomic and
 deterministic (docs/DETERMINISM.md), side by side.
@@ -254,6 +254,36 @@ def bench_sgd():
               f"{t*1e6:8.1f} us  {nbytes*numel/t/1e9:7.0f} GB/s")
 
 
+def bench_mix(passes=3):
+    """batch_mix next to the ATen composition it replaces, alternated in one
+    session. Bytes are computed from the shape: the fused mixup reads x twice
+    and writes once (3 tensors), CutMix reads and writes once (the box is
+    read from the partner INSTEAD of the sample itself: 2 tensors). ATen's
+    mixup is flip (2) + two muls (2 + 2) + add (3) = 9 tensors, its CutMix
+    flip (2) + where (3, plus the broadcast mask) = 5."""
+    print("== batch_mix vs ATen composition (256, 3, 224, 224) bf16 "
+          "channels_last ==")
+    x = _cl(torch.randn(256, 3, 224, 224, device=DEV, dtype=torch.bfloat16))
+    nb = x.numel() * 2
+    lam = 0.3
+    h, w = x.shape[2], x.shape[3]
+    box = (37, 37 + 112, 51, 51 + 112)  # a quarter of the image, odd offsets
+    inside = torch.zeros(1, 1, h, w, dtype=torch.bool, device=DEV)
+    inside[:, :, box[0]:box[1], box[2]:box[3]] = True
+    rows = [
+        ("mixup  fused", lambda: e.batch_mix(x, 0, lam, 0, 0, 0, 0), 3 * nb),
+        ("mixup  aten ", lambda: x * lam + x.flip(0) * (1 - lam), 9 * nb),
+        ("cutmix fused", lambda: e.batch_mix(x, 1, 1.0, *box), 2 * nb),
+        ("cutmix aten ", lambda: torch.where(inside, x.flip(0), x),
+         5 * nb + inside.numel()),
+    ]
+    for p in range(passes):
+        for name, fn, moved in rows:
+            t = timeit(fn, iters=500, warmup=20)  # windows of 12-60 ms
+            print(f"pass {p} {name} {t*1e6:8.1f} us  {moved/1e6:7.1f} MB "
+                  f"{moved/t/1e9:7.0f} GB/s")
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     deterministic = "--deterministic" in args
@@ -272,3 +302,5 @@ if __name__ == "__main__":
         bench_gemm()
     if "sgd" in groups or "all" in groups:
         bench_sgd()
+    if "mix" in groups or "all" in groups:
+        bench_mix()

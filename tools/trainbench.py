@@ -47,6 +47,16 @@ def parse_args():
     p.add_argument("--im-size", type=int, default=224)
     p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
                    help="OPTIM.OPTIMIZER: fused SGD-momentum, or LARS on it")
+    p.add_argument("--label-smooth", type=float, default=0.0,
+                   help="TRAIN.LABEL_SMOOTH")
+    p.add_argument("--mixup-alpha", type=float, default=0.0,
+                   help="TRAIN.MIXUP_ALPHA")
+    p.add_argument("--cutmix-alpha", type=float, default=0.0,
+                   help="TRAIN.CUTMIX_ALPHA")
+    p.add_argument("--mix-prob", type=float, default=1.0,
+                   help="TRAIN.MIX_PROB")
+    p.add_argument("--mix-switch-prob", type=float, default=0.5,
+                   help="TRAIN.MIX_SWITCH_PROB")
     p.add_argument("--modes", default="eager,captured",
                    help="comma list; one mode alone is for profiling it")
     return p.parse_args()
@@ -64,7 +74,6 @@ def main():
     from distribuuuu_amd import utils
     from distribuuuu_amd.data import DeviceSyntheticLoader
     from distribuuuu_amd.graph_step import GraphedTrainStep
-    from distribuuuu_amd.ops import functional as DF
 
     use_bf16 = args.dtype == "bf16" and has_gpu
     batch = args.batch if has_gpu else 8
@@ -79,6 +88,11 @@ def main():
     cfg.OPTIM.BASE_LR = args.lr
     cfg.OPTIM.OPTIMIZER = args.optimizer
     cfg.OPTIM.WARMUP_EPOCHS = 0
+    cfg.TRAIN.LABEL_SMOOTH = args.label_smooth
+    cfg.TRAIN.MIXUP_ALPHA = args.mixup_alpha
+    cfg.TRAIN.CUTMIX_ALPHA = args.cutmix_alpha
+    cfg.TRAIN.MIX_PROB = args.mix_prob
+    cfg.TRAIN.MIX_SWITCH_PROB = args.mix_switch_prob
     cfg.OUT_DIR = os.environ.get("BENCH_OUT_DIR", "/tmp/bench_out")
     cfg.freeze()
 
@@ -86,7 +100,9 @@ def main():
     torch.manual_seed(1234)
     net = T.build_network(device)
     optimizer = utils.construct_optimizer(net)
-    runner = GraphedTrainStep(net, DF.cross_entropy, optimizer,
+    # DF.cross_entropy itself unless a soft-target flag is set
+    criterion = T.build_criterion()
+    runner = GraphedTrainStep(net, criterion, optimizer,
                               cfg.TRAIN.TOPK, device=device, dtype=dtype)
 
     # built once, outside every timed window (its batch is drawn on the host)
@@ -99,7 +115,7 @@ def main():
         cfg.TRAIN.PRINT_FREQ = print_freq
         cfg.freeze()
         loader.length = n
-        T.train_epoch(loader, net, DF.cross_entropy, optimizer, 0, device,
+        T.train_epoch(loader, net, criterion, optimizer, 0, device,
                       dtype, graph_step=runner if graphed else None)
         if has_gpu:
             torch.cuda.synchronize()
@@ -145,6 +161,9 @@ def main():
         "print_freq": args.print_freq,
         "lr": args.lr,
         "optimizer": args.optimizer,
+        "label_smooth": args.label_smooth,
+        "mixup_alpha": args.mixup_alpha,
+        "cutmix_alpha": args.cutmix_alpha,
         "weights_finite": finite,
         "runner": runner.stats,
     }))
