@@ -101,6 +101,9 @@ at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
 std::vector<at::Tensor> conv2d_fwd_bn(at::Tensor x, at::Tensor w, int64_t sh,
                                       int64_t sw, int64_t ph, int64_t pw,
                                       int64_t dh, int64_t dw, int64_t groups);
+std::vector<at::Tensor> conv2d_fwd_halo_dbg(at::Tensor x, at::Tensor w,
+                                            bool emit, bool halo);
+bool conv3x3_halo_admits(int64_t N, int64_t H, int64_t W);
 at::Tensor conv2d_dgrad(at::Tensor gy, at::Tensor w, int64_t H, int64_t W,
                         int64_t sh, int64_t sw, int64_t ph, int64_t pw,
                         int64_t dh, int64_t dw, int64_t groups);
@@ -242,6 +245,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_fwd", &conv2d_fwd);
   m.def("conv2d_fwd_v1", &conv2d_fwd_v1);
   m.def("conv2d_fwd_bn", &conv2d_fwd_bn);
+  m.def("conv2d_fwd_halo_dbg", &conv2d_fwd_halo_dbg, py::arg("x"),
+        py::arg("w"), py::arg("emit"), py::arg("halo"));
+  m.def("conv3x3_halo_admits", &conv3x3_halo_admits);
   m.def("conv2d_dgrad", &conv2d_dgrad);
   m.def("conv2d_dgrad_bn", &conv2d_dgrad_bn);
   m.def("conv2d_dgrad_acc", &conv2d_dgrad_acc);

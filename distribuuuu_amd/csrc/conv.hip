@@ -974,11 +974,19 @@ at::Tensor conv2d_fwd_v2_flat(at::Tensor x, at::Tensor wp, int64_t Kt_,
                               at::Tensor* part_out, const BnBwdEmit* bemit,
                               at::Tensor* acc_into = nullptr);
 
+// conv_halo.hip: halo-staged 3x3 / stride 1 / pad 1 / 64->64 kernel
+bool conv3x3_halo_admits(int64_t N, int64_t H, int64_t W);
+void conv3x3_halo_launch(const at::Tensor& x, const at::Tensor& w,
+                         at::Tensor& y, const at::Tensor& zbuf, float* part);
+
+// halo_force: -1 = the dispatcher's own choice, 0 / 1 = force the 3x3 64->64
+// route off / on (conv2d_fwd_halo_dbg)
 static at::Tensor conv2d_fwd_impl(at::Tensor x, at::Tensor w, int64_t sh,
                                   int64_t sw, int64_t ph, int64_t pw,
                                   int64_t dh, int64_t dw, int64_t groups,
                                   at::Tensor* part_out,
-                                  const BnBwdEmit* bemit = nullptr) {
+                                  const BnBwdEmit* bemit = nullptr,
+                                  int halo_force = -1) {
   const int N = x.size(0), H = x.size(2), W = x.size(3);
   const int Kt = w.size(0), R = w.size(2), S = w.size(3);
   // v2 (3-slot glds ring) wins when the reduction is deep enough to fill
@@ -1080,6 +1088,29 @@ static at::Tensor conv2d_fwd_impl(at::Tensor x, at::Tensor w, int64_t sh,
     sp.part = nullptr;
     const dim3 skg((int)((sp.M + 255) / 256));
     if (bemit != nullptr) part_out = nullptr;  // smallk: no bwd emission
+    // 3x3 / stride 1 / pad 1 / 64->64: input tile + halo staged in LDS once
+    // instead of nine global reads per pixel (conv_halo.hip); bit-identical
+    static const bool halo_off = []() {
+      const char* e = getenv("DISTRIBUUUU_CONV_HALO");
+      return e && e[0] == '0';
+    }();
+    const bool halo_fits =
+        C_ == 64 && R == 3 && S == 3 && sh == 1 && sw == 1 && ph == 1 &&
+        pw == 1 && x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+        w.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+        conv3x3_halo_admits(N, H, W);
+    TORCH_CHECK(halo_force != 1 || halo_fits,
+                "conv2d_fwd: shape outside the halo kernel's gate");
+    if (halo_force == 1 || (halo_force < 0 && !halo_off && halo_fits)) {
+      float* hp = nullptr;
+      if (part_out != nullptr) {
+        *part_out = at::empty({(int64_t)skg.x, 128},
+                              x.options().dtype(at::kFloat));
+        hp = part_out->data_ptr<float>();
+      }
+      conv3x3_halo_launch(x, w, y, zbuf, hp);
+      return y;
+    }
     if (part_out != nullptr) {
       *part_out = at::empty({(int64_t)skg.x, 128},
                             x.options().dtype(at::kFloat));
@@ -1124,6 +1155,19 @@ at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
                       int64_t ph, int64_t pw, int64_t dh, int64_t dw,
                       int64_t groups) {
   return conv2d_fwd_impl(x, w, sh, sw, ph, pw, dh, dw, groups, nullptr);
+}
+
+// Debug/benchmark entry: the dispatcher's launch for a small-K conv with the
+// halo route forced on or off, so both kernels run in one process (the env
+// knobs are read once). 3x3 / stride 1 / pad 1. Returns {y} or {y, part}.
+std::vector<at::Tensor> conv2d_fwd_halo_dbg(at::Tensor x, at::Tensor w,
+                                            bool emit, bool halo) {
+  at::Tensor part;
+  auto y = conv2d_fwd_impl(x, w, 1, 1, 1, 1, 1, 1, 1, emit ? &part : nullptr,
+                           nullptr, halo ? 1 : 0);
+  if (!emit) return {y};
+  TORCH_CHECK(part.defined(), "conv2d_fwd_halo_dbg: route without partials");
+  return {y, part};
 }
 
 // conv forward + BN sum/sumsq partials emitted from the epilogue (F1):

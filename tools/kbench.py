@@ -99,6 +99,24 @@ def bench_conv():
             t2 = timeit(lambda: e.conv2d_dgrad(gy, wt, h, w, s, s, p, p, 1, 1, 1))
             line += f" | dgrad {t2*1e6:8.1f} us {flops/t2/1e12:6.1f} TF"
         print(line)
+        if (c, k, r, s) == (64, 64, 3, 1) and e.conv3x3_halo_admits(n, h, w):
+            _bench_halo_routes(x, wt, flops)
+
+
+def _bench_halo_routes(x, wt, flops, passes=3):
+    """3x3 64->64: global-fed kernel vs halo-staged kernel, alternated, through
+    the debug entry that forces the route. The dgrad is the same launch with
+    the flipped weight."""
+    wf = e.weight_flip_t(wt, 1)
+    nbytes = 2 * x.numel() * 2 + wt.numel() * 2
+    for i in range(passes):
+        for name, wgt in (("fwd", wt), ("dgrad", wf)):
+            row = f"  pass {i} {name:5s}"
+            for label, halo in (("old", False), ("halo", True)):
+                t = timeit(lambda: e.conv2d_fwd_halo_dbg(x, wgt, False, halo))
+                row += (f" | {label:4s} {t*1e6:7.1f} us {flops/t/1e12:6.1f} TF"
+                        f" {nbytes/t/1e9:6.0f} GB/s")
+            print(row)
 
 
 def bench_wgrad(deterministic=False):
