@@ -16,29 +16,8 @@
 // boundary predication (zero-fill); one-step software pipeline (T14 G15:
 // loads for step k+1 issued before compute of step k, LDS write after the
 // barrier).
-#include "common.h"
-
-// v2 minimum reduction depth R*S*Cg (DISTRIBUUUU_V2_MINRSC, default 512):
-// below this the 3-slot glds ring has too few k-steps to spin up.
-static int v2_minrsc() {
-  static const int v = []() {
-    const char* e = getenv("DISTRIBUUUU_V2_MINRSC");
-    return e ? atoi(e) : 512;
-  }();
-  return v;
-}
-
-// separate depth floor for the scatter/accumulate fwd_into route (proj and
-// residual-fork dgrads) so it can be swept independently of the main
-// forward dispatch
-static int v2_into_minrsc() {
-  static const int v = []() {
-    const char* e = getenv("DISTRIBUUUU_V2INTO_MINRSC");
-    return e ? atoi(e) : v2_minrsc();
-  }();
-  return v;
-}
-
+#include "conv_common.h"
+#include "conv_route.h"
 
 typedef __attribute__((ext_vector_type(8))) short short8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -856,28 +835,38 @@ __global__ __launch_bounds__(256) void conv_smallk_pipe_kernel(
 // ---------------------------------------------------------------------------
 // host wrappers
 // ---------------------------------------------------------------------------
-// fp32 kernel path (conv_fp32.hip)
-at::Tensor conv2d_fwd_into_fp32(at::Tensor x, at::Tensor w, at::Tensor y,
-                                int64_t Ho, int64_t Wo, int64_t sh, int64_t sw,
-                                int64_t ph, int64_t pw, int64_t dh, int64_t dw,
-                                int64_t groups, int64_t osh, int64_t osw,
-                                int64_t oh0, int64_t ow0,
-                                at::Tensor* part_out);
+// one launch per kernel family: each picks the instantiation from its flags
+static void launch_v1(const ConvParams& p, dim3 grid, int emode, bool acc) {
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, cur_stream(), p);
+  };
+  if (emode == 2) go(conv_igemm_fwd_kernel<2>);
+  else if (emode == 1) go(conv_igemm_fwd_kernel<1>);
+  else if (acc) go(conv_igemm_fwd_kernel<0, true>);
+  else go(conv_igemm_fwd_kernel<0>);
+}
 
-// BN-backward stat emission (EMODE 2) descriptor: the conv being launched is
-// a DGRAD whose output is the gy of the BatchNorm that produced this conv's
-// logical input; x/scale/shift/act describe that BN.
-struct BnBwdEmit {
-  const __hip_bfloat16* x;
-  const float* scale;
-  const float* shift;
-  int act;
-};
+// small 1x1 GEMM family: the register-cached C = 64 / 32 kernels, else generic
+template <bool EMIT>
+static void launch_small_gemm(const SmallGemmParams& p, dim3 grid) {
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, cur_stream(), p);
+  };
+  if (p.C == 64) go(conv_gemm_smallc_kernel<2, EMIT>);
+  else if (p.C == 32) go(conv_gemm_smallc_kernel<1, EMIT>);
+  else go(conv_gemm_small_kernel<EMIT>);
+}
 
-at::Tensor conv2d_fwd_v2_into(at::Tensor x, at::Tensor w, at::Tensor y,
-                              int64_t Ho, int64_t Wo, int64_t groups,
-                              int64_t osh, int64_t osw, int64_t oh0,
-                              int64_t ow0, bool acc = false);
+// K = 64 patch family: the pipelined C = 64 / 32 kernels, else generic
+template <bool EMIT>
+static void launch_smallk(const SmallConvParams& p, dim3 grid) {
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, cur_stream(), p);
+  };
+  if (p.C == 64) go(conv_smallk_pipe_kernel<2, EMIT>);
+  else if (p.C == 32) go(conv_smallk_pipe_kernel<1, EMIT>);
+  else go(conv_smallk_kernel<EMIT>);
+}
 
 at::Tensor conv2d_fwd_into(at::Tensor x, at::Tensor w, at::Tensor y, int64_t Ho,
                            int64_t Wo, int64_t sh, int64_t sw, int64_t ph,
@@ -895,16 +884,13 @@ at::Tensor conv2d_fwd_into(at::Tensor x, at::Tensor w, at::Tensor y, int64_t Ho,
   {
     // deep pad-free windows (parity-decomposed / strided dgrads) ride the
     // v2 glds ring with the scatter epilogue instead of the v1 tile kernel
-    static const bool v2i_off = []() {
-      const char* e = getenv("DISTRIBUUUU_CONV_V2INTO");
-      return e && e[0] == '0';
-    }();
+    const ConvGates& gates = conv_gates();
     const int Cgi = w.size(1), Ri = w.size(2), Si = w.size(3);
     const int Kgi = (int)(w.size(0) / groups);
-    if (!v2i_off && part_out == nullptr && bemit == nullptr && ph == 0 &&
+    if (gates.v2into && part_out == nullptr && bemit == nullptr && ph == 0 &&
         pw == 0 && sh == 1 && sw == 1 && dh == 1 && dw == 1 &&
         (Si * Cgi) % 64 == 0 && Kgi >= 96 &&
-        (int64_t)Ri * Si * Cgi >= v2_into_minrsc() && Cgi % 8 == 0 &&
+        (int64_t)Ri * Si * Cgi >= gates.v2into_minrsc && Cgi % 8 == 0 &&
         Ho + Ri - 1 <= x.size(2) && Wo + Si - 1 <= x.size(3))
       return conv2d_fwd_v2_into(x, w, y, Ho, Wo, groups, osh, osw, oh0, ow0,
                                 acc);
@@ -937,47 +923,21 @@ at::Tensor conv2d_fwd_into(at::Tensor x, at::Tensor w, at::Tensor y, int64_t Ho,
   p.bnshift = nullptr;
   p.bnact = 0;
   dim3 grid(p.tiles_m, (Kg + BN - 1) / BN, groups);
-  if (bemit != nullptr) {
+  const int emode = bemit != nullptr ? 2 : part_out != nullptr ? 1 : 0;
+  if (emode != 0) {
     *part_out = at::empty({(int64_t)p.tiles_m, (int64_t)2 * Kt},
                           x.options().dtype(at::kFloat));
     p.part = part_out->data_ptr<float>();
+  }
+  if (bemit != nullptr) {
     p.bnx = bemit->x;
     p.bnscale = bemit->scale;
     p.bnshift = bemit->shift;
     p.bnact = bemit->act;
-    hipLaunchKernelGGL(conv_igemm_fwd_kernel<2>, grid, dim3(256), 0,
-                       cur_stream(), p);
-  } else if (part_out != nullptr) {
-    *part_out = at::empty({(int64_t)p.tiles_m, (int64_t)2 * Kt},
-                          x.options().dtype(at::kFloat));
-    p.part = part_out->data_ptr<float>();
-    hipLaunchKernelGGL(conv_igemm_fwd_kernel<1>, grid, dim3(256), 0,
-                       cur_stream(), p);
-  } else if (acc) {
-    hipLaunchKernelGGL((conv_igemm_fwd_kernel<0, true>), grid, dim3(256), 0,
-                       cur_stream(), p);
-  } else {
-    hipLaunchKernelGGL(conv_igemm_fwd_kernel<0>, grid, dim3(256), 0,
-                       cur_stream(), p);
   }
+  launch_v1(p, grid, emode, acc);
   return y;
 }
-
-at::Tensor conv2d_fwd_v2p(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
-                          int64_t ph, int64_t pw, int64_t dh, int64_t dw,
-                          int64_t groups, at::Tensor* part_out,
-                          const BnBwdEmit* bemit = nullptr);
-at::Tensor conv2d_fwd_v2_flat(at::Tensor x, at::Tensor wp, int64_t Kt_,
-                              int64_t Cg_, int64_t R_, int64_t S_, int64_t sh,
-                              int64_t sw, int64_t ph, int64_t pw, int64_t dh,
-                              int64_t dw, int64_t groups,
-                              at::Tensor* part_out, const BnBwdEmit* bemit,
-                              at::Tensor* acc_into = nullptr);
-
-// conv_halo.hip: halo-staged 3x3 / stride 1 / pad 1 / 64->64 kernel
-bool conv3x3_halo_admits(int64_t N, int64_t H, int64_t W);
-void conv3x3_halo_launch(const at::Tensor& x, const at::Tensor& w,
-                         at::Tensor& y, const at::Tensor& zbuf, float* part);
 
 // halo_force: -1 = the dispatcher's own choice, 0 / 1 = force the 3x3 64->64
 // route off / on (conv2d_fwd_halo_dbg)
@@ -991,30 +951,14 @@ static at::Tensor conv2d_fwd_impl(at::Tensor x, at::Tensor w, int64_t sh,
   const int Kt = w.size(0), R = w.size(2), S = w.size(3);
   // v2 (3-slot glds ring) wins when the reduction is deep enough to fill
   // its pipeline; v1 handles shallow-K, small-K and grouped shapes.
-  static const bool v2_off = []() {
-    const char* e = getenv("DISTRIBUUUU_CONV_V2");
-    return e && e[0] == '0';
-  }();
+  const ConvGates& gates = conv_gates();
   const int C_ = x.size(1);
-  // per-group geometry decides the ring gate: deep-enough reduction fills
-  // the 3-slot pipeline (RegNetY's 232-wide groups qualify: Kg=232,
-  // R*S*Cg=2088)
-  const int v2Kg = Kt / (int)groups;
-  const int v2Cg = C_ / (int)groups;
-  static const int v2_mink = []() {
-    const char* e = getenv("DISTRIBUUUU_V2_MINK");
-    return e ? atoi(e) : 192;
-  }();
-  if (!v2_off && v2Kg >= v2_mink &&
-      (int64_t)R * S * v2Cg >= v2_minrsc() &&
-      v2Cg % 8 == 0 && x.scalar_type() == at::kBFloat16)
+  // per-group geometry decides the ring gate (v2_ring_ok)
+  if (v2_ring_ok(Kt / (int)groups, C_ / (int)groups, R, S,
+                 x.scalar_type() == at::kBFloat16))
     return conv2d_fwd_v2p(x, w, sh, sw, ph, pw, dh, dw, groups, part_out,
                           bemit);
-  static const bool small_off = []() {
-    const char* e = getenv("DISTRIBUUUU_CONV_SMALL");
-    return e && e[0] == '0';
-  }();
-  if (!small_off && groups == 1 && R == 1 && S == 1 && sh == 1 && sw == 1 &&
+  if (gates.small && groups == 1 && R == 1 && S == 1 && sh == 1 && sw == 1 &&
       C_ % 32 == 0 && Kt % 64 == 0 && x.scalar_type() == at::kBFloat16 &&
       ((C_ <= 64 && Kt <= 512) || (C_ <= 256 && Kt <= 64))) {
     const int64_t M = (int64_t)N * H * W;
@@ -1032,29 +976,14 @@ static at::Tensor conv2d_fwd_impl(at::Tensor x, at::Tensor w, int64_t sh,
       *part_out = at::empty({(int64_t)sg.x, (int64_t)2 * Kt},
                             x.options().dtype(at::kFloat));
       sp.part = part_out->data_ptr<float>();
-      if (C_ == 64)
-        hipLaunchKernelGGL((conv_gemm_smallc_kernel<2, true>), sg, dim3(256),
-                           0, cur_stream(), sp);
-      else if (C_ == 32)
-        hipLaunchKernelGGL((conv_gemm_smallc_kernel<1, true>), sg, dim3(256),
-                           0, cur_stream(), sp);
-      else
-        hipLaunchKernelGGL(conv_gemm_small_kernel<true>, sg, dim3(256), 0,
-                           cur_stream(), sp);
-    } else if (C_ == 64)
-      hipLaunchKernelGGL((conv_gemm_smallc_kernel<2, false>), sg, dim3(256),
-                         0, cur_stream(), sp);
-    else if (C_ == 32)
-      hipLaunchKernelGGL((conv_gemm_smallc_kernel<1, false>), sg, dim3(256),
-                         0, cur_stream(), sp);
-    else
-      hipLaunchKernelGGL(conv_gemm_small_kernel<false>, sg, dim3(256), 0,
-                         cur_stream(), sp);
+    }
+    sp.part ? launch_small_gemm<true>(sp, sg)
+            : launch_small_gemm<false>(sp, sg);
     return y;
   }
   const int Ho = (H + 2 * ph - dh * (R - 1) - 1) / sh + 1;
   const int Wo = (W + 2 * pw - dw * (S - 1) - 1) / sw + 1;
-  if (!small_off && groups == 1 && Kt == 64 && C_ <= 64 && C_ % 8 == 0 &&
+  if (gates.small && groups == 1 && Kt == 64 && C_ <= 64 && C_ % 8 == 0 &&
       dh == 1 && dw == 1 && R * S > 1 && R * S * C_ <= 1024 &&
       x.scalar_type() == at::kBFloat16) {
     const int RSC = R * S * C_;
@@ -1090,10 +1019,6 @@ static at::Tensor conv2d_fwd_impl(at::Tensor x, at::Tensor w, int64_t sh,
     if (bemit != nullptr) part_out = nullptr;  // smallk: no bwd emission
     // 3x3 / stride 1 / pad 1 / 64->64: input tile + halo staged in LDS once
     // instead of nine global reads per pixel (conv_halo.hip); bit-identical
-    static const bool halo_off = []() {
-      const char* e = getenv("DISTRIBUUUU_CONV_HALO");
-      return e && e[0] == '0';
-    }();
     const bool halo_fits =
         C_ == 64 && R == 3 && S == 3 && sh == 1 && sw == 1 && ph == 1 &&
         pw == 1 && x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
@@ -1101,7 +1026,7 @@ static at::Tensor conv2d_fwd_impl(at::Tensor x, at::Tensor w, int64_t sh,
         conv3x3_halo_admits(N, H, W);
     TORCH_CHECK(halo_force != 1 || halo_fits,
                 "conv2d_fwd: shape outside the halo kernel's gate");
-    if (halo_force == 1 || (halo_force < 0 && !halo_off && halo_fits)) {
+    if (halo_force == 1 || (halo_force < 0 && gates.halo && halo_fits)) {
       float* hp = nullptr;
       if (part_out != nullptr) {
         *part_out = at::empty({(int64_t)skg.x, 128},
@@ -1115,24 +1040,8 @@ static at::Tensor conv2d_fwd_impl(at::Tensor x, at::Tensor w, int64_t sh,
       *part_out = at::empty({(int64_t)skg.x, 128},
                             x.options().dtype(at::kFloat));
       sp.part = part_out->data_ptr<float>();
-      if (C_ == 64)
-        hipLaunchKernelGGL((conv_smallk_pipe_kernel<2, true>), skg, dim3(256),
-                           0, cur_stream(), sp);
-      else if (C_ == 32)
-        hipLaunchKernelGGL((conv_smallk_pipe_kernel<1, true>), skg, dim3(256),
-                           0, cur_stream(), sp);
-      else
-        hipLaunchKernelGGL(conv_smallk_kernel<true>, skg, dim3(256), 0,
-                           cur_stream(), sp);
-    } else if (C_ == 64)
-      hipLaunchKernelGGL((conv_smallk_pipe_kernel<2, false>), skg, dim3(256),
-                         0, cur_stream(), sp);
-    else if (C_ == 32)
-      hipLaunchKernelGGL((conv_smallk_pipe_kernel<1, false>), skg, dim3(256),
-                         0, cur_stream(), sp);
-    else
-      hipLaunchKernelGGL(conv_smallk_kernel<false>, skg, dim3(256), 0,
-                         cur_stream(), sp);
+    }
+    sp.part ? launch_smallk<true>(sp, skg) : launch_smallk<false>(sp, skg);
     return y;
   }
   auto y = at::empty({N, Kt, Ho, Wo},
@@ -1373,171 +1282,172 @@ at::Tensor pad_channels(at::Tensor x, int64_t Cn) {
   return y;
 }
 
-// dgrad: gx = conv(dilate(gy), flipT(w)) written into a zeroed [H, W] canvas
-static at::Tensor conv2d_dgrad_impl(at::Tensor gy, at::Tensor w, int64_t H,
-                                    int64_t W, int64_t sh, int64_t sw,
-                                    int64_t ph, int64_t pw, int64_t dh,
-                                    int64_t dw, int64_t groups,
-                                    at::Tensor* part_out,
-                                    const BnBwdEmit* bemit,
-                                    const at::Tensor* pre = nullptr,
-                                    int64_t pre_kind = -1) {
+// ---------------------------------------------------------------------------
+// dgrad: dgrad_route (conv_route.h) decides, conv2d_dgrad_run executes
+// ---------------------------------------------------------------------------
+// `into` (may be null) is a candidate accumulate buffer; it qualifies when it
+// is a bf16 channels_last tensor of exactly gx's shape.
+static DgradRoute dgrad_route_of(const at::Tensor& gy, const at::Tensor& w,
+                                 int64_t H, int64_t W, int64_t sh, int64_t sw,
+                                 int64_t ph, int64_t pw, int64_t dh,
+                                 int64_t dw, int64_t groups,
+                                 const at::Tensor* into) {
+  const bool into_ok =
+      into != nullptr && into->scalar_type() == at::kBFloat16 &&
+      into->is_contiguous(at::MemoryFormat::ChannelsLast) &&
+      into->sizes() ==
+          at::IntArrayRef({gy.size(0), w.size(1) * groups, H, W});
+  return dgrad_route(gy.size(1), w.size(1), w.size(2), w.size(3), sh, sw, ph,
+                     pw, dh, dw, groups,
+                     gy.scalar_type() == at::kBFloat16, into_ok);
+}
+
+// gx = conv(dilate(gy), flipT(w)), computed the way `rt` says. With rt.acc
+// the epilogue adds gx into *into (ACC epilogues exist in the v1 and v2
+// kernels only) and *into is returned; otherwise gx is a fresh tensor.
+// pre / pre_kind: an already-transformed weight (conv2d_dgrad_prep), used
+// when its kind is the one the route needs.
+static at::Tensor conv2d_dgrad_run(DgradRoute rt, at::Tensor gy, at::Tensor w,
+                                   int64_t H, int64_t W, int64_t sh,
+                                   int64_t sw, int64_t ph, int64_t pw,
+                                   int64_t dh, int64_t dw, int64_t groups,
+                                   at::Tensor* part_out,
+                                   const BnBwdEmit* bemit,
+                                   const at::Tensor* pre = nullptr,
+                                   int64_t pre_kind = -1,
+                                   at::Tensor* into = nullptr) {
   CHECK_GPU(gy);
   check_nhwc(gy, "gy");
+  const bool acc = rt.acc;
+  TORCH_CHECK(!acc || (into && !part_out && !bemit),
+              "dgrad: acc needs a buffer and excludes partial emission");
   const int N = gy.size(0);
   const int Cg = w.size(1), R = w.size(2), S = w.size(3);
   const int Ct = Cg * groups;
-  {
-    // same-size dgrad on the v2 ring: ONE fused flip+span-pad weight pass
-    // (the generic path below would flip then pad separately)
-    const int Kt0 = gy.size(1);
-    const int dKg0 = Ct / (int)groups;
-    const int dCg0 = Kt0 / (int)groups;
-    static const int v2mink2 = []() {
-      const char* e = getenv("DISTRIBUUUU_V2_MINK");
-      return e ? atoi(e) : 192;
-    }();
-    static const bool v2off2 = []() {
-      const char* e = getenv("DISTRIBUUUU_CONV_V2");
-      return e && e[0] == '0';
-    }();
-    // any ph <= dh*(R-1) works at stride 1: the as-fwd conv with pad
-    // dh*(R-1)-ph lands on the conv-input size exactly (ph = 0 is the
-    // padded-canvas BN fusion's dgrad)
-    if (sh == 1 && sw == 1 && dh * (R - 1) >= ph &&
-        dw * (S - 1) >= pw && Kt0 % (8 * (int)groups) == 0 && !v2off2 &&
-        dKg0 >= v2mink2 && (int64_t)R * S * dCg0 >= v2_minrsc() &&
-        dCg0 % 8 == 0 &&
-        gy.scalar_type() == at::kBFloat16) {
-      const int SPAN64 = ((int)(S * dCg0) + 63) / 64 * 64;
-      auto wsp = (pre != nullptr && pre_kind == 1)
-                     ? *pre
-                     : weight_flip_t_span(w, groups, SPAN64);
-      return conv2d_fwd_v2_flat(gy, wsp, Ct, dCg0, R, S, 1, 1,
-                                dh * (R - 1) - ph, dw * (S - 1) - pw, dh, dw,
-                                groups, part_out, bemit);
-    }
+  // padding of the stride-1 as-forward conv
+  const int pph = dh * (R - 1) - ph, ppw = dw * (S - 1) - pw;
+  auto canvas = [&]() {
+    return at::empty({N, Ct, H, W}, gy.options().memory_format(
+                                        at::MemoryFormat::ChannelsLast));
+  };
+  if (rt.kind == DgradKind::V2Same) {
+    // ONE fused flip+span-pad weight pass feeds the ring directly
+    const int fCg = gy.size(1) / (int)groups;
+    const int SPAN64 = ((int)(S * fCg) + 63) / 64 * 64;
+    auto wsp = (pre != nullptr && pre_kind == 1)
+                   ? *pre
+                   : weight_flip_t_span(w, groups, SPAN64);
+    return conv2d_fwd_v2_flat(gy, wsp, Ct, fCg, R, S, 1, 1, pph, ppw, dh, dw,
+                              groups, part_out, bemit, acc ? into : nullptr);
   }
   auto wt = (pre != nullptr && pre_kind == 0)
                 ? *pre
                 : weight_flip_t(w, groups);  // [Ct, Kg, R, S] cl
-  if (R == 1 && S == 1 && (sh > 1 || sw > 1) && ph == 0 && pw == 0) {
-    // strided-output GEMM: gx[ho*sh, wo*sw] = gy[ho, wo] @ w^T, rest zero.
-    // The zeroed gap positions contribute g = 0 to the BN-backward sums, so
-    // partials over written positions alone are the full sums.
-    auto gx1 = at::empty({N, Ct, H, W}, gy.options().memory_format(
-                                            at::MemoryFormat::ChannelsLast));
-    gx1.zero_();
-    conv2d_fwd_into(gy, wt, gx1, gy.size(2), gy.size(3), 1, 1, 0, 0, 1, 1,
-                    groups, sh, sw, 0, 0, part_out, bemit);
-    return gx1;
-  }
-  if (R == 3 && S == 3 && sh == 2 && sw == 2 && dh == 1 && dw == 1 &&
-      ph == 1 && pw == 1) {
-    // parity decomposition: for stride-2 with pad 1, each output-parity
-    // class (h%2, w%2) of gx receives only the taps of matching parity —
-    // four small {1,2}x{1,2}-tap convs over gy scattered with stride 2
-    // instead of a 3x3 conv over 2x-dilated (3/4-zero) gy. Derivation: for
-    // h = 2u + h0, ho = u + e with e = (h0 + 1 - r)/2, so the e-ordered tap
-    // weights are flipT(w) rows (1 - h0)::2.
-    auto gx = at::empty({N, Ct, H, W}, gy.options().memory_format(
-                                           at::MemoryFormat::ChannelsLast));
-    std::vector<at::Tensor> parts;
-    for (int h0 = 0; h0 < 2; ++h0) {
-      const int64_t hu = (H - h0 + 1) >> 1;
-      auto wr = (h0 == 0) ? wt.slice(2, 1, 2) : wt.slice(2, 0, 3, 2);
-      for (int w0 = 0; w0 < 2; ++w0) {
-        const int64_t wu = (W - w0 + 1) >> 1;
-        auto wsub = ((w0 == 0) ? wr.slice(3, 1, 2) : wr.slice(3, 0, 3, 2))
-                        .contiguous(at::MemoryFormat::ChannelsLast);
-        at::Tensor sub_part;
-        conv2d_fwd_into(gy, wsub, gx, hu, wu, 1, 1, 0, 0, 1, 1, groups, 2, 2,
-                        h0, w0, bemit ? &sub_part : nullptr, bemit);
-        if (bemit && sub_part.defined()) parts.push_back(sub_part);
-      }
+  switch (rt.kind) {
+    case DgradKind::Strided1x1: {
+      // strided-output GEMM: gx[ho*sh, wo*sw] = gy[ho, wo] @ w^T, rest zero.
+      // The zeroed gap positions contribute g = 0 to the BN-backward sums,
+      // so partials over written positions alone are the full sums. With
+      // acc the gaps receive no main-branch gradient: `into` already holds
+      // their final values.
+      at::Tensor gx = acc ? *into : canvas();
+      if (!acc) gx.zero_();
+      conv2d_fwd_into(gy, wt, gx, gy.size(2), gy.size(3), 1, 1, 0, 0, 1, 1,
+                      groups, sh, sw, 0, 0, part_out, bemit, acc);
+      return gx;
     }
-    if (bemit && part_out && parts.size() == 4)
-      *part_out = at::cat(parts, 0);
-    return gx;
+    case DgradKind::Parity3x3: {
+      // parity decomposition: for stride-2 with pad 1, each output-parity
+      // class (h%2, w%2) of gx receives only the taps of matching parity —
+      // four small {1,2}x{1,2}-tap convs over gy scattered with stride 2
+      // instead of a 3x3 conv over 2x-dilated (3/4-zero) gy. Derivation:
+      // for h = 2u + h0, ho = u + e with e = (h0 + 1 - r)/2, so the
+      // e-ordered tap weights are flipT(w) rows (1 - h0)::2. The four
+      // classes tile gx disjointly, so with acc each sub-conv
+      // scatter-accumulates its own positions exactly once.
+      at::Tensor gx = acc ? *into : canvas();
+      std::vector<at::Tensor> parts;
+      for (int h0 = 0; h0 < 2; ++h0) {
+        const int64_t hu = (H - h0 + 1) >> 1;
+        auto wr = (h0 == 0) ? wt.slice(2, 1, 2) : wt.slice(2, 0, 3, 2);
+        for (int w0 = 0; w0 < 2; ++w0) {
+          const int64_t wu = (W - w0 + 1) >> 1;
+          auto wsub = ((w0 == 0) ? wr.slice(3, 1, 2) : wr.slice(3, 0, 3, 2))
+                          .contiguous(at::MemoryFormat::ChannelsLast);
+          at::Tensor sub_part;
+          conv2d_fwd_into(gy, wsub, gx, hu, wu, 1, 1, 0, 0, 1, 1, groups, 2,
+                          2, h0, w0, bemit ? &sub_part : nullptr, bemit, acc);
+          if (bemit && sub_part.defined()) parts.push_back(sub_part);
+        }
+      }
+      if (bemit && part_out && parts.size() == 4)
+        *part_out = at::cat(parts, 0);
+      return gx;
+    }
+    case DgradKind::Same:
+      // same-size conv. Fresh output: the plain fwd dispatcher applies and
+      // reaches the small and halo kernels. acc: the v1 predicated kernel.
+      if (acc)
+        return conv2d_fwd_into(gy, wt, *into, H, W, 1, 1, pph, ppw, dh, dw,
+                               groups, 1, 1, 0, 0, nullptr, nullptr, true);
+      return conv2d_fwd_impl(gy, wt, 1, 1, pph, ppw, dh, dw, groups, part_out,
+                             bemit);
+    default: {
+      auto gyd = (sh == 1 && sw == 1) ? gy : dilate_nhwc(gy, sh, sw);
+      TORCH_CHECK(pph >= 0 && ppw >= 0, "dgrad pad underflow");
+      // Every input row/col receives its own output: run the conv at
+      // logical output size exactly (H, W); the kernel's bounds predication
+      // supplies the zero-padding of the dilated gy on both ends (incl. rows
+      // past the last forward window, where forward's floor division
+      // dropped input).
+      auto gx = canvas();
+      conv2d_fwd_into(gyd, wt, gx, H, W, 1, 1, pph, ppw, dh, dw, groups, 1, 1,
+                      0, 0, part_out, bemit);
+      return gx;
+    }
   }
-  const int Kt_ = gy.size(1);
-  if (sh == 1 && sw == 1 && dh * (R - 1) >= ph && dw * (S - 1) >= pw &&
-      (R > 1 || (ph == 0 && pw == 0)) &&
-      (groups == 1 || Kt_ % (8 * groups) == 0)) {
-    // same-size conv: the plain fwd path applies (the v2-eligible shapes
-    // were already taken above with the fused weight transform)
-    return conv2d_fwd_impl(gy, wt, 1, 1, dh * (R - 1) - ph,
-                           dw * (S - 1) - pw, dh, dw, groups, part_out,
-                           bemit);
-  }
-  (void)Kt_;
-  auto gyd = (sh == 1 && sw == 1) ? gy : dilate_nhwc(gy, sh, sw);
-  const int Hd = gyd.size(2), Wd = gyd.size(3);
-  const int pph = dh * (R - 1) - ph, ppw = dw * (S - 1) - pw;
-  TORCH_CHECK(pph >= 0 && ppw >= 0, "dgrad pad underflow");
-  // Every input row/col receives its own output: run the conv at logical
-  // output size exactly (H, W); the kernel's bounds predication supplies the
-  // zero-padding of the dilated gy on both ends (incl. rows past the last
-  // forward window, where forward's floor division dropped input).
-  (void)Hd; (void)Wd;
-  auto gx = at::empty({N, Ct, H, W}, gy.options().memory_format(
-                                           at::MemoryFormat::ChannelsLast));
-  conv2d_fwd_into(gyd, wt, gx, H, W, 1, 1, pph, ppw, dh, dw, groups, 1, 1, 0,
-                  0, part_out, bemit);
-  return gx;
 }
 
+// pre / pre_kind: what conv2d_dgrad_prep returned for this weight, if any
 at::Tensor conv2d_dgrad(at::Tensor gy, at::Tensor w, int64_t H, int64_t W,
                         int64_t sh, int64_t sw, int64_t ph, int64_t pw,
-                        int64_t dh, int64_t dw, int64_t groups) {
-  return conv2d_dgrad_impl(gy, w, H, W, sh, sw, ph, pw, dh, dw, groups,
-                           nullptr, nullptr);
+                        int64_t dh, int64_t dw, int64_t groups,
+                        c10::optional<at::Tensor> pre, int64_t pre_kind) {
+  return conv2d_dgrad_run(
+      dgrad_route_of(gy, w, H, W, sh, sw, ph, pw, dh, dw, groups, nullptr),
+      gy, w, H, W, sh, sw, ph, pw, dh, dw, groups, nullptr, nullptr,
+      pre.has_value() ? &*pre : nullptr, pre_kind);
 }
 
 // Forward-time dgrad weight-transform precompute (launched on a side
 // stream during the forward pass so backward's critical path skips the
-// flip kernels). Returns {transformed_weight, kind}: kind 1 = span-padded
-// flat flip for the same-size v2 ring, kind 0 = plain flipT. The gate
-// mirrors conv2d_dgrad_impl's v2 dispatch exactly.
-std::vector<at::Tensor> conv2d_dgrad_prep(at::Tensor w, int64_t Kt0,
-                                          int64_t sh, int64_t sw, int64_t ph,
-                                          int64_t pw, int64_t dh, int64_t dw,
-                                          int64_t groups) {
-  const int Cg = w.size(1), R = w.size(2), S = w.size(3);
-  const int Ct = Cg * (int)groups;
-  const int dKg0 = Ct / (int)groups;
-  const int dCg0 = (int)(Kt0 / groups);
-  static const int v2mink4 = []() {
-    const char* e = getenv("DISTRIBUUUU_V2_MINK");
-    return e ? atoi(e) : 192;
-  }();
-  static const bool v2off4 = []() {
-    const char* e = getenv("DISTRIBUUUU_CONV_V2");
-    return e && e[0] == '0';
-  }();
-  int64_t kind = 0;
-  at::Tensor out;
-  if (sh == 1 && sw == 1 && dh * (R - 1) >= ph &&
-      dw * (S - 1) >= pw && Kt0 % (8 * groups) == 0 && !v2off4 &&
-      dKg0 >= v2mink4 && (int64_t)R * S * dCg0 >= v2_minrsc() &&
-      dCg0 % 8 == 0 &&
-      w.scalar_type() == at::kBFloat16) {
-    const int SPAN64 = ((int)(S * dCg0) + 63) / 64 * 64;
-    out = weight_flip_t_span(w, groups, SPAN64);
-    kind = 1;
-  } else {
-    out = weight_flip_t(w, groups);
+// flip kernels). Returns {transformed_weight, kind}: the kind is the
+// route's wkind (1 = span-padded flat flip, 0 = plain flipT).
+std::tuple<at::Tensor, int64_t> conv2d_dgrad_prep(
+    at::Tensor w, int64_t Kt0, int64_t sh, int64_t sw, int64_t ph,
+    int64_t pw, int64_t dh, int64_t dw, int64_t groups) {
+  const int S = w.size(3);
+  const int wkind =
+      dgrad_route(Kt0, w.size(1), w.size(2), S, sh, sw, ph, pw, dh, dw,
+                  groups, w.scalar_type() == at::kBFloat16, false)
+          .wkind;
+  if (wkind == 1) {
+    const int SPAN64 = (S * (int)(Kt0 / groups) + 63) / 64 * 64;
+    return {weight_flip_t_span(w, groups, SPAN64), 1};
   }
-  return {out, at::scalar_tensor(kind)};
+  return {weight_flip_t(w, groups), 0};
 }
 
-at::Tensor conv2d_dgrad_pre(at::Tensor gy, at::Tensor w, int64_t H,
-                            int64_t W, int64_t sh, int64_t sw, int64_t ph,
-                            int64_t pw, int64_t dh, int64_t dw,
-                            int64_t groups, at::Tensor pre,
-                            int64_t pre_kind) {
-  return conv2d_dgrad_impl(gy, w, H, W, sh, sw, ph, pw, dh, dw, groups,
-                           nullptr, nullptr, &pre, pre_kind);
+// The route a dgrad with these operands takes, as (name, wkind, acc);
+// launches nothing (shapes and dtypes only, so meta tensors work).
+std::tuple<std::string, int64_t, bool> conv2d_dgrad_route(
+    at::Tensor gy, at::Tensor w, int64_t H, int64_t W, int64_t sh, int64_t sw,
+    int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t groups,
+    c10::optional<at::Tensor> into) {
+  const DgradRoute rt =
+      dgrad_route_of(gy, w, H, W, sh, sw, ph, pw, dh, dw, groups,
+                     into.has_value() ? &*into : nullptr);
+  return {dgrad_kind_name(rt.kind), rt.wkind, rt.acc};
 }
 
 // dgrad + BN-backward stat partials (docs/DESIGN_bn_conv_fusion.md, the
@@ -1558,9 +1468,10 @@ std::vector<at::Tensor> conv2d_dgrad_bn(at::Tensor gy, at::Tensor w,
   em.shift = bnshift.data_ptr<float>();
   em.act = (int)bnact;
   at::Tensor part;
-  auto gx = conv2d_dgrad_impl(gy, w, H, W, sh, sw, ph, pw, dh, dw, groups,
-                              &part, &em);
   // (pre-transform not threaded here: the EMODE-2 path is opt-in/off)
+  auto gx = conv2d_dgrad_run(
+      dgrad_route_of(gy, w, H, W, sh, sw, ph, pw, dh, dw, groups, nullptr),
+      gy, w, H, W, sh, sw, ph, pw, dh, dw, groups, &part, &em);
   if (!part.defined()) part = at::empty({0, 0}, bnscale.options());
   return {gx, part};
 }
@@ -1570,87 +1481,17 @@ std::vector<at::Tensor> conv2d_dgrad_bn(at::Tensor gy, at::Tensor w,
 // fork branch's already-computed gradient — inside the dgrad epilogue
 // (+1 read stream) instead of autograd's separate 2-read/1-write
 // elementwise add over the whole gx. Returns {tensor, flag}: flag 1 means
-// `into` now holds the sum; flag 0 means the dispatched route has no ACC
-// epilogue and the returned tensor is a FRESH gx (caller must add).
+// `into` now holds the sum; flag 0 means the route has no ACC epilogue and
+// the returned tensor is a FRESH gx (caller must add).
 std::tuple<at::Tensor, int64_t> conv2d_dgrad_acc(
     at::Tensor gy, at::Tensor w, int64_t H, int64_t W, int64_t sh, int64_t sw,
     int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t groups,
-    at::Tensor into, c10::optional<at::Tensor> pre_opt = c10::nullopt,
-    int64_t pre_kind = -1) {
-  const at::Tensor* pre = pre_opt.has_value() ? &*pre_opt : nullptr;
-  CHECK_GPU(gy);
-  const int N = gy.size(0);
-  const int Cg = w.size(1), R = w.size(2), S = w.size(3);
-  const int Ct = Cg * groups;
-  const int Kt0 = gy.size(1);
-  const int dKg0 = Ct / (int)groups;
-  const int dCg0 = Kt0 / (int)groups;
-  const bool same_size = sh == 1 && sw == 1 && dh * (R - 1) >= ph &&
-                         dw * (S - 1) >= pw &&
-                         (R > 1 || (ph == 0 && pw == 0));
-  static const int v2mink3 = []() {
-    const char* e = getenv("DISTRIBUUUU_V2_MINK");
-    return e ? atoi(e) : 192;
-  }();
-  static const bool v2off3 = []() {
-    const char* e = getenv("DISTRIBUUUU_CONV_V2");
-    return e && e[0] == '0';
-  }();
-  if (gy.scalar_type() == at::kBFloat16 && groups == 1 && dCg0 % 8 == 0 &&
-      into.scalar_type() == at::kBFloat16 &&
-      into.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-      into.sizes() == at::IntArrayRef({(int64_t)N, (int64_t)Ct, H, W})) {
-    if (same_size && !v2off3 && Kt0 % 8 == 0 && dKg0 >= v2mink3 &&
-        (int64_t)R * S * dCg0 >= v2_minrsc()) {
-      const int SPAN64 = ((int)(S * dCg0) + 63) / 64 * 64;
-      auto wsp = (pre != nullptr && pre_kind == 1)
-                     ? *pre
-                     : weight_flip_t_span(w, 1, SPAN64);
-      conv2d_fwd_v2_flat(gy, wsp, Ct, dCg0, R, S, 1, 1, dh * (R - 1) - ph,
-                         dw * (S - 1) - pw, dh, dw, 1, nullptr, nullptr,
-                         &into);
-      return {into, 1};
-    }
-    if (same_size) {
-      auto wt = (pre != nullptr && pre_kind == 0) ? *pre
-                                                   : weight_flip_t(w, 1);
-      conv2d_fwd_into(gy, wt, into, H, W, 1, 1, dh * (R - 1) - ph,
-                      dw * (S - 1) - pw, dh, dw, 1, 1, 1, 0, 0, nullptr,
-                      nullptr, true);
-      return {into, 1};
-    }
-    if (R == 1 && S == 1 && (sh > 1 || sw > 1) && ph == 0 && pw == 0) {
-      // strided 1x1 proj: scatter-accumulate at (ho*sh, wo*sw); the gap
-      // positions receive no main-branch gradient, so `into` already holds
-      // their final values.
-      auto wt = (pre != nullptr && pre_kind == 0) ? *pre
-                                                   : weight_flip_t(w, 1);
-      conv2d_fwd_into(gy, wt, into, gy.size(2), gy.size(3), 1, 1, 0, 0, 1, 1,
-                      1, sh, sw, 0, 0, nullptr, nullptr, true);
-      return {into, 1};
-    }
-    if (R == 3 && S == 3 && sh == 2 && sw == 2 && dh == 1 && dw == 1 &&
-        ph == 1 && pw == 1) {
-      // parity decomposition (see conv2d_dgrad_impl): the four parity
-      // classes tile gx disjointly, so each sub-conv scatter-accumulates
-      // its own positions exactly once.
-      auto wt = (pre != nullptr && pre_kind == 0) ? *pre
-                                                   : weight_flip_t(w, 1);
-      for (int h0 = 0; h0 < 2; ++h0) {
-        const int64_t hu = (H - h0 + 1) >> 1;
-        auto wr = (h0 == 0) ? wt.slice(2, 1, 2) : wt.slice(2, 0, 3, 2);
-        for (int w0 = 0; w0 < 2; ++w0) {
-          const int64_t wu = (W - w0 + 1) >> 1;
-          auto wsub = ((w0 == 0) ? wr.slice(3, 1, 2) : wr.slice(3, 0, 3, 2))
-                          .contiguous(at::MemoryFormat::ChannelsLast);
-          conv2d_fwd_into(gy, wsub, into, hu, wu, 1, 1, 0, 0, 1, 1, 1, 2, 2,
-                          h0, w0, nullptr, nullptr, true);
-        }
-      }
-      return {into, 1};
-    }
-  }
-  auto gx = conv2d_dgrad_impl(gy, w, H, W, sh, sw, ph, pw, dh, dw, groups,
-                              nullptr, nullptr, pre, pre_kind);
-  return {gx, 0};
+    at::Tensor into, c10::optional<at::Tensor> pre, int64_t pre_kind) {
+  const DgradRoute rt =
+      dgrad_route_of(gy, w, H, W, sh, sw, ph, pw, dh, dw, groups, &into);
+  auto gx = conv2d_dgrad_run(rt, gy, w, H, W, sh, sw, ph, pw, dh, dw, groups,
+                             nullptr, nullptr,
+                             pre.has_value() ? &*pre : nullptr, pre_kind,
+                             &into);
+  return {gx, rt.acc ? 1 : 0};
 }

@@ -8,7 +8,7 @@
 // (pad_weight_span), so every gather address is in-bounds and span-tail
 // garbage in A multiplies a zero in B. M/K tile tails clamp their source rows
 // (garbage rows are computed but never stored).
-#include "common.h"
+#include "conv_common.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4c;
 typedef __bf16 bf16x8c __attribute__((ext_vector_type(8)));
@@ -376,12 +376,51 @@ __global__ void pad_weight_span_kernel(const T* __restrict__ w,
 
 }  // namespace
 
-struct BnBwdEmit {
-  const __hip_bfloat16* x;
-  const float* scale;
-  const float* shift;
-  int act;
-};
+// Everything but the stride/dilation (default 1) and the output scatter
+// (default: y is the dense [N, Kt, Ho, Wo] output). xin is x itself or its
+// padded flat copy [N, Hp, Wp, Ct] (+slack).
+static Conv2Params fill_v2_params(const at::Tensor& xin, const at::Tensor& wp,
+                                  const at::Tensor& y, int N, int Hp, int Wp,
+                                  int Ct, int Cg, int Kg, int R, int S,
+                                  int SPAN64, int Ho, int Wo) {
+  Conv2Params p;
+  p.x = (const __hip_bfloat16*)xin.data_ptr();
+  p.w = (const __hip_bfloat16*)wp.data_ptr();
+  p.xend8 = (const __hip_bfloat16*)xin.data_ptr() + xin.numel() - 8;
+  p.y = (__hip_bfloat16*)y.data_ptr();
+  p.N = N; p.Hp = Hp; p.Wp = Wp; p.C = Cg; p.K = Kg;
+  p.Ct = Ct; p.Kt = y.size(1);
+  p.R = R; p.SPAN64 = SPAN64; p.Cg = Cg; p.S = S;
+  p.sh = 1; p.sw = 1; p.dh = 1; p.dw = 1;
+  p.Ho = Ho; p.Wo = Wo;
+  p.HoA = y.size(2); p.WoA = y.size(3);
+  p.osh = 1; p.osw = 1; p.oh0 = 0; p.ow0 = 0;
+  p.M = N * Ho * Wo;
+  p.nspan = SPAN64 / BK2;
+  p.ksteps = R * p.nspan;
+  p.tiles_m = (p.M + BM2 - 1) / BM2;
+  p.part = nullptr;
+  p.bnx = nullptr; p.bnscale = nullptr; p.bnshift = nullptr; p.bnact = 0;
+  return p;
+}
+
+// the one v2 launch: picks the (EMODE, CLAMP, ACC) instantiation
+template <int EMODE, bool ACC = false>
+static void launch_v2_clamp(const Conv2Params& p, dim3 grid, bool clamp) {
+  if (clamp)
+    hipLaunchKernelGGL((conv_igemm_v2_kernel<EMODE, true, ACC>), grid,
+                       dim3(512), 0, cur_stream(), p);
+  else
+    hipLaunchKernelGGL((conv_igemm_v2_kernel<EMODE, false, ACC>), grid,
+                       dim3(512), 0, cur_stream(), p);
+}
+static void launch_v2(const Conv2Params& p, dim3 grid, int emode, bool clamp,
+                      bool acc) {
+  if (emode == 2) launch_v2_clamp<2>(p, grid, clamp);
+  else if (emode == 1) launch_v2_clamp<1>(p, grid, clamp);
+  else if (acc) launch_v2_clamp<0, true>(p, grid, clamp);
+  else launch_v2_clamp<0>(p, grid, clamp);
+}
 
 // Core launcher taking the weight ALREADY in span-padded flat [Kt, R,
 // SPAN64] form (either from pad_weight_span or the fused dgrad
@@ -391,7 +430,7 @@ at::Tensor conv2d_fwd_v2_flat(at::Tensor x, at::Tensor wp, int64_t Kt_,
                               int64_t sw, int64_t ph, int64_t pw, int64_t dh,
                               int64_t dw, int64_t groups,
                               at::Tensor* part_out, const BnBwdEmit* bemit,
-                              at::Tensor* acc_into = nullptr) {
+                              at::Tensor* acc_into) {
   CHECK_GPU(x);
   TORCH_CHECK(x.scalar_type() == at::kBFloat16, "v2: bf16 only");
   check_nhwc(x, "x");
@@ -441,66 +480,23 @@ at::Tensor conv2d_fwd_v2_flat(at::Tensor x, at::Tensor wp, int64_t Kt_,
     y = at::empty({N, Kt, Ho, Wo},
                   x.options().memory_format(at::MemoryFormat::ChannelsLast));
   }
-  Conv2Params p;
-  p.x = (const __hip_bfloat16*)xin.data_ptr();
-  p.w = (const __hip_bfloat16*)wp.data_ptr();
-  p.xend8 = (const __hip_bfloat16*)xin.data_ptr() + xin.numel() - 8;
-  p.y = (__hip_bfloat16*)y.data_ptr();
-  p.N = N; p.Hp = Hp; p.Wp = Wp; p.C = C; p.K = K;
-  p.Ct = Ct; p.Kt = Kt;
-  p.R = R; p.SPAN64 = SPAN64; p.Cg = C; p.S = S;
+  Conv2Params p =
+      fill_v2_params(xin, wp, y, N, Hp, Wp, Ct, C, K, R, S, SPAN64, Ho, Wo);
   p.sh = sh; p.sw = sw; p.dh = dh; p.dw = dw;
-  p.Ho = Ho; p.Wo = Wo;
-  p.HoA = Ho; p.WoA = Wo; p.osh = 1; p.osw = 1; p.oh0 = 0; p.ow0 = 0;
-  p.M = N * Ho * Wo;
-  p.nspan = SPAN64 / BK2;
-  p.ksteps = R * p.nspan;
-  p.tiles_m = (p.M + BM2 - 1) / BM2;
-  p.part = nullptr;
-  p.bnx = nullptr;
-  p.bnscale = nullptr;
-  p.bnshift = nullptr;
-  p.bnact = 0;
   dim3 grid(p.tiles_m, (K + BN2 - 1) / BN2, groups);
-  if (bemit != nullptr) {
+  const int emode = bemit != nullptr ? 2 : part_out != nullptr ? 1 : 0;
+  if (emode != 0) {
     *part_out = at::empty({(int64_t)p.tiles_m, (int64_t)2 * Kt},
                           x.options().dtype(at::kFloat));
     p.part = part_out->data_ptr<float>();
+  }
+  if (bemit != nullptr) {
     p.bnx = bemit->x;
     p.bnscale = bemit->scale;
     p.bnshift = bemit->shift;
     p.bnact = bemit->act;
-    if (clamp_tail)
-      hipLaunchKernelGGL((conv_igemm_v2_kernel<2, true>), grid, dim3(512), 0,
-                         cur_stream(), p);
-    else
-      hipLaunchKernelGGL(conv_igemm_v2_kernel<2>, grid, dim3(512), 0,
-                         cur_stream(), p);
-  } else if (part_out != nullptr) {
-    *part_out = at::empty({(int64_t)p.tiles_m, (int64_t)2 * Kt},
-                          x.options().dtype(at::kFloat));
-    p.part = part_out->data_ptr<float>();
-    if (clamp_tail)
-      hipLaunchKernelGGL((conv_igemm_v2_kernel<1, true>), grid, dim3(512), 0,
-                         cur_stream(), p);
-    else
-      hipLaunchKernelGGL(conv_igemm_v2_kernel<1>, grid, dim3(512), 0,
-                         cur_stream(), p);
-  } else if (acc_into != nullptr) {
-    if (clamp_tail)
-      hipLaunchKernelGGL((conv_igemm_v2_kernel<0, true, true>), grid,
-                         dim3(512), 0, cur_stream(), p);
-    else
-      hipLaunchKernelGGL((conv_igemm_v2_kernel<0, false, true>), grid,
-                         dim3(512), 0, cur_stream(), p);
-  } else {
-    if (clamp_tail)
-      hipLaunchKernelGGL((conv_igemm_v2_kernel<0, true>), grid, dim3(512), 0,
-                         cur_stream(), p);
-    else
-      hipLaunchKernelGGL(conv_igemm_v2_kernel<0>, grid, dim3(512), 0,
-                         cur_stream(), p);
   }
+  launch_v2(p, grid, emode, clamp_tail, acc_into != nullptr);
   return y;
 }
 
@@ -537,37 +533,17 @@ at::Tensor conv2d_fwd_v2(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
 at::Tensor conv2d_fwd_v2_into(at::Tensor x, at::Tensor w, at::Tensor y,
                               int64_t Ho, int64_t Wo, int64_t groups,
                               int64_t osh, int64_t osw, int64_t oh0,
-                              int64_t ow0, bool acc = false) {
+                              int64_t ow0, bool acc) {
   const int N = x.size(0), Ct = x.size(1), H = x.size(2), W = x.size(3);
   const int Kt = w.size(0), Cg = w.size(1), R = w.size(2), S = w.size(3);
-  const int C = Cg, K = Kt / (int)groups;
+  const int K = Kt / (int)groups;
   const int SC = S * Cg;
   TORCH_CHECK(SC % BK2 == 0, "v2_into: span must be 64-aligned");
-  Conv2Params p;
-  p.x = (const __hip_bfloat16*)x.data_ptr();
-  p.w = (const __hip_bfloat16*)w.data_ptr();
-  p.xend8 = (const __hip_bfloat16*)x.data_ptr() + x.numel() - 8;
-  p.y = (__hip_bfloat16*)y.data_ptr();
-  p.N = N; p.Hp = H; p.Wp = W; p.C = C; p.K = K;
-  p.Ct = Ct; p.Kt = y.size(1);
-  p.R = R; p.SPAN64 = SC; p.Cg = C; p.S = S;
-  p.sh = 1; p.sw = 1; p.dh = 1; p.dw = 1;
-  p.Ho = Ho; p.Wo = Wo;
-  p.HoA = y.size(2); p.WoA = y.size(3);
-  p.osh = osh; p.osw = osw; p.oh0 = oh0; p.ow0 = ow0;
-  p.M = N * Ho * Wo;
-  p.nspan = SC / BK2;
-  p.ksteps = R * p.nspan;
-  p.tiles_m = (p.M + BM2 - 1) / BM2;
-  p.part = nullptr;
-  p.bnx = nullptr; p.bnscale = nullptr; p.bnshift = nullptr; p.bnact = 0;
   TORCH_CHECK(Ho + R - 1 <= H && Wo + S - 1 <= W, "v2_into: window OOB");
+  Conv2Params p =
+      fill_v2_params(x, w, y, N, H, W, Ct, Cg, K, R, S, SC, Ho, Wo);
+  p.osh = osh; p.osw = osw; p.oh0 = oh0; p.ow0 = ow0;
   dim3 grid(p.tiles_m, (K + BN2 - 1) / BN2, groups);
-  if (acc)
-    hipLaunchKernelGGL((conv_igemm_v2_kernel<0, false, true>), grid, dim3(512),
-                       0, cur_stream(), p);
-  else
-    hipLaunchKernelGGL(conv_igemm_v2_kernel<0>, grid, dim3(512), 0,
-                       cur_stream(), p);
+  launch_v2(p, grid, 0, false, acc);
   return y;
 }

@@ -126,10 +126,9 @@ class _HIPConv2d(torch.autograd.Function):
                 cur = torch.cuda.current_stream()
                 ts.wait_stream(cur)
                 with torch.cuda.stream(ts):
-                    wt_pre, kt = e.conv2d_dgrad_prep(
+                    wt_pre, wt_kind = e.conv2d_dgrad_prep(
                         w, kout, stride[0], stride[1], padding[0],
                         padding[1], dilation[0], dilation[1], groups)
-                wt_kind = int(kt.item())
                 wt_ev = torch.cuda.Event()
                 wt_ev.record(ts)
         ctx.wt_pre = (wt_pre, wt_kind, wt_ev)
@@ -176,37 +175,29 @@ class _HIPConv2d(torch.autograd.Function):
                     pre.record_stream(torch.cuda.current_stream())
             fslot = ctx.fork_slot
             fbuf = fslot.get("g") if fslot is not None else None
+            geom = (gyp, wd, x.shape[2], x.shape[3], stride[0], stride[1],
+                    padding[0], padding[1], dilation[0], dilation[1], groups)
             if fbuf is not None and not cpad and fbuf.dtype == gyp.dtype:
                 # residual fork (see _Fork): the other branch's gradient is
                 # already in fbuf — accumulate this dgrad into it inside the
                 # epilogue (one extra read stream) instead of letting
                 # autograd run a separate whole-tensor add
                 gx, acc_done = e.conv2d_dgrad_acc(
-                    gyp, wd, x.shape[2], x.shape[3], stride[0], stride[1],
-                    padding[0], padding[1], dilation[0], dilation[1], groups,
-                    fbuf, pre, pkind if pre is not None else -1)
+                    *geom, fbuf, pre, pkind if pre is not None else -1)
             elif ctx.bnslot is not None and len(saved) == 5:
                 # dgrad + BN-backward stats from the same epilogue: the
                 # consuming BN reads the partials IF this gx arrives there
                 # unmodified (data_ptr identity check in its backward)
                 bnx, bnscale, bnshift = saved[2], saved[3], saved[4]
-                gx, bpart = e.conv2d_dgrad_bn(
-                    gyp, wd, x.shape[2], x.shape[3], stride[0], stride[1],
-                    padding[0], padding[1], dilation[0], dilation[1], groups,
-                    bnx, bnscale, bnshift, ctx.bnact)
+                gx, bpart = e.conv2d_dgrad_bn(*geom, bnx, bnscale, bnshift,
+                                              ctx.bnact)
                 if bpart.numel():
                     ctx.bnslot["parts"].append(bpart)
                     ctx.bnslot["gx"] = gx
             elif pre is not None:
-                gx = e.conv2d_dgrad_pre(gyp, wd, x.shape[2], x.shape[3],
-                                        stride[0], stride[1], padding[0],
-                                        padding[1], dilation[0], dilation[1],
-                                        groups, pre, pkind)
+                gx = e.conv2d_dgrad(*geom, pre, pkind)
             else:
-                gx = e.conv2d_dgrad(gyp, wd, x.shape[2], x.shape[3],
-                                    stride[0], stride[1], padding[0],
-                                    padding[1], dilation[0], dilation[1],
-                                    groups)
+                gx = e.conv2d_dgrad(*geom)
             if cpad:
                 gx = _cl(gx[:, :cin])
             if fslot is not None and fbuf is None:

@@ -509,9 +509,9 @@ def test_fork_grads_match_unforked():
 
 @pytest.mark.gpu
 def test_dgrad_pre_transform_matches():
-    """conv2d_dgrad_prep's route gate must stay in sync with
-    conv2d_dgrad_impl's dispatch: feeding the precomputed transform back in
-    (conv2d_dgrad_pre) must reproduce conv2d_dgrad exactly."""
+    """conv2d_dgrad_prep's weight kind must be the one conv2d_dgrad's route
+    consumes: feeding the precomputed transform back in (conv2d_dgrad's
+    pre / pre_kind) must reproduce the plain conv2d_dgrad exactly."""
     e = _ext()
     cl = torch.channels_last
     # (C, H, K, R, stride, pad): v2 same-size, small same-size, strided
@@ -529,8 +529,8 @@ def test_dgrad_pre_transform_matches():
                          dtype=torch.bfloat16).contiguous(memory_format=cl)
         w = (torch.randn(k, c, r, r, device="cuda", dtype=torch.bfloat16)
              * 0.05).contiguous(memory_format=cl)
-        pre, kindt = e.conv2d_dgrad_prep(w, k, s, s, pad, pad, 1, 1, 1)
+        pre, kind = e.conv2d_dgrad_prep(w, k, s, s, pad, pad, 1, 1, 1)
         ref = e.conv2d_dgrad(gy, w, h, h, s, s, pad, pad, 1, 1, 1)
-        got = e.conv2d_dgrad_pre(gy, w, h, h, s, s, pad, pad, 1, 1, 1,
-                                 pre, int(kindt.item()))
+        got = e.conv2d_dgrad(gy, w, h, h, s, s, pad, pad, 1, 1, 1,
+                             pre, int(kind))
         assert torch.equal(ref, got), (c, h, k, r, s, pad)
