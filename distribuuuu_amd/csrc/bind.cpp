@@ -137,6 +137,9 @@ at::Tensor pad_channels(at::Tensor x, int64_t Cn);
 at::Tensor conv2d_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
                         int64_t sh, int64_t sw, int64_t ph, int64_t pw,
                         int64_t dh, int64_t dw, int64_t groups);
+std::tuple<std::string, int64_t, int64_t, std::string> conv2d_wgrad_route(
+    at::Tensor gy, at::Tensor x, int64_t R, int64_t S, int64_t sh, int64_t sw,
+    int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t groups);
 // depthwise.hip
 at::Tensor dwconv_fwd(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
                       int64_t ph, int64_t pw);
@@ -259,6 +262,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_dgrad_acc", &conv2d_dgrad_acc);
   m.def("conv2d_dgrad_prep", &conv2d_dgrad_prep);
   m.def("conv2d_wgrad", &conv2d_wgrad);
+  m.def("conv2d_wgrad_route", &conv2d_wgrad_route);
   m.def("gemm_nt", &gemm_nt);
   m.def("conv2d_fwd_v2", &conv2d_fwd_v2);
   m.def("weight_flip_t", &weight_flip_t);

@@ -11,12 +11,17 @@
 // q, q+4, q+8, q+12). The v1 element-scatter staging was 8-way bank-conflict
 // bound (SQ_LDS_BANK_CONFLICT = 83% of LDS cycles).
 //
-// Split-m: each block owns a pixel chunk and atomically accumulates its fp32
-// partial tile into gw_accum[Kt][R*S*Cg]; a final cast kernel emits bf16.
-// Deterministic mode (docs/DETERMINISM.md): each block instead stores its
-// partial into slot `chunk` of a [chunks][Kt*R*S*Cg] workspace and
-// ordered_reduce (det_reduce.hip) sums the slots in order and emits bf16.
+// Split-m: each block owns a pixel chunk. How the chunks' fp32 partial tiles
+// meet is decided per launch by wgrad_route (wgrad_route.h):
+//   atomic — atomicAdd into a zeroed gw_accum[Kt][R*S*Cg]; a cast kernel
+//            emits bf16 (memset + atomics + cast).
+//   slab   — the DET = true instantiation: plain stores into slot `chunk` of
+//            a [chunks][Kt*R*S*Cg] workspace; ordered_reduce (det_reduce.hip)
+//            sums the slots in order and emits bf16. Deterministic mode
+//            (docs/DETERMINISM.md) always runs this; the default mode picks
+//            it where it measured faster than the atomic chain.
 #include "common.h"
+#include "wgrad_route.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4w;
 typedef __bf16 bf16x8w __attribute__((ext_vector_type(8)));
@@ -25,8 +30,8 @@ namespace {
 
 constexpr int WBM = 64;   // k rows per tile
 constexpr int WBN = 64;   // rsc cols per tile
-constexpr int WBK = 64;   // pixels per k-step
-constexpr int CHUNK_STEPS = 64;  // k-steps per block chunk (4096 pixels)
+constexpr int WBK = WG_STEP_PIX;   // pixels per k-step
+constexpr int CHUNK_STEPS = WG_CHUNK_STEPS;  // k-steps per block chunk
 // [32 m][16 col] subtile: 32 rows x 32 B = 1024 B, padded to 1056 B so the
 // 8-lane b128 write groups land on distinct banks (264 dwords % 32 = 8).
 constexpr int SUBT = 1056;
@@ -901,28 +906,14 @@ __global__ void cast_acc_kernel(const float* __restrict__ acc,
     gw[i] = from_f32<__hip_bfloat16>(acc[i]);
 }
 
-// Deterministic-mode workspace cap for the kernels whose split-m chunk is a
-// runtime value (tr128, ring128): their csteps grows until
-// chunks * Kt * RSC * 4 bytes fits (or one chunk is left).
-constexpr int64_t DET_WS_CAP = (int64_t)64 << 20;
-
-int det_grow_csteps(int csteps, int64_t M64, int64_t slot_elems) {
-  auto nchunks = [&](int cs) {
-    return (M64 + (int64_t)cs * WBK - 1) / ((int64_t)cs * WBK);
-  };
-  while (nchunks(csteps) > 1 && nchunks(csteps) * slot_elems * 4 > DET_WS_CAP)
-    csteps *= 2;
-  return csteps;
-}
-
 // fp32 accumulator of one wgrad launch: a zeroed [Kt, RSC] buffer for the
-// atomic epilogue, or in deterministic mode a [chunks][Kt*RSC] workspace
-// (no memset: every slot is written in full). Both come from the caching
+// atomic epilogue, or for a slab launch a [chunks][Kt*RSC] workspace (no
+// memset: every slot is written in full). Both come from the caching
 // allocator, so they are safe on the wgrad side stream and under capture.
 at::Tensor wg_acc_alloc(const at::Tensor& x, int64_t Kt, int64_t RSC,
-                        int64_t chunks, bool det, int64_t* pstride) {
+                        int64_t chunks, bool slab, int64_t* pstride) {
   auto opts = x.options().dtype(at::kFloat);
-  if (det) {
+  if (slab) {
     *pstride = Kt * RSC;
     return at::empty({chunks, Kt * RSC}, opts);
   }
@@ -932,15 +923,15 @@ at::Tensor wg_acc_alloc(const at::Tensor& x, int64_t Kt, int64_t RSC,
   return acc;
 }
 
-// bf16 gw from the accumulator: cast pass (atomic mode) or the ordered
-// reduction over chunks, which emits bf16 itself (deterministic mode)
+// bf16 gw from the accumulator: cast pass (atomic) or the ordered reduction
+// over the chunks' slots, which emits bf16 itself (slab)
 at::Tensor wg_emit_gw(const at::Tensor& x, const at::Tensor& acc, int64_t Kt,
                       int64_t Cg, int64_t R, int64_t S, int64_t chunks,
-                      bool det) {
+                      bool slab) {
   auto gw = at::empty({Kt, Cg, R, S},
                       x.options().memory_format(at::MemoryFormat::ChannelsLast));
   const int64_t total = Kt * R * S * Cg;
-  if (det)
+  if (slab)
     ordered_reduce<__hip_bfloat16>(acc.data_ptr<float>(),
                                    (__hip_bfloat16*)gw.data_ptr(), (int)chunks,
                                    total, 1.f);
@@ -951,11 +942,66 @@ at::Tensor wg_emit_gw(const at::Tensor& x, const at::Tensor& acc, int64_t Kt,
   return gw;
 }
 
+// zero-padded copy of x for the glds ring kernels, which predicate nothing
+at::Tensor wg_pad_image(const at::Tensor& x, int N, int H, int W, int Ct,
+                        int ph, int pw) {
+  const int Hp = H + 2 * ph, Wp = W + 2 * pw;
+  auto xp = at::empty({(int64_t)N * Hp * Wp * Ct}, x.options());
+  hipLaunchKernelGGL((wg_pad_image_kernel<__hip_bfloat16>),
+                     dim3((Wp * Ct / 8 + 255) / 256, N * Hp), dim3(256), 0,
+                     cur_stream(), (const __hip_bfloat16*)x.data_ptr(),
+                     (__hip_bfloat16*)xp.data_ptr(), N, H, W, Ct, Hp, Wp, ph,
+                     pw);
+  return xp;
+}
+
+struct WgradGeom {
+  int N, Ct, H, W, Kt, Ho, Wo, Cg, Kg;
+  int64_t M;
+};
+
+// shape checks shared by the executor and the classify-only binding; reads
+// sizes and dtypes only, so it runs on meta tensors
+WgradGeom wgrad_geom(const at::Tensor& gy, const at::Tensor& x,
+                     int64_t groups) {
+  TORCH_CHECK(gy.scalar_type() == at::kBFloat16, "wgrad: bf16/fp32 only");
+  check_nhwc(gy, "gy");
+  check_nhwc(x, "x");
+  WgradGeom s;
+  s.N = x.size(0); s.Ct = x.size(1); s.H = x.size(2); s.W = x.size(3);
+  s.Kt = gy.size(1); s.Ho = gy.size(2); s.Wo = gy.size(3);
+  s.Cg = s.Ct / groups; s.Kg = s.Kt / groups;
+  TORCH_CHECK(s.Cg % 8 == 0 && s.Kg % 8 == 0,
+              "wgrad: Cg/Kg must be multiples of 8");
+  s.M = (int64_t)s.N * s.Ho * s.Wo;
+  return s;
+}
+
+WgradRoute wgrad_route_of(const WgradGeom& s, int64_t R, int64_t S,
+                          int64_t groups) {
+  const WgradGates gates = read_wgrad_gates();  // re-read per call
+  TORCH_CHECK(gates.acc != -2,
+              "DISTRIBUUUU_WGRAD_ACC must be auto, atomic or slab");
+  // is_deterministic() is sampled per launch
+  return wgrad_route(s.M, s.Kg, s.Cg, (int)R, (int)S, groups,
+                     is_deterministic(), gates);
+}
+
 }  // namespace
 
 at::Tensor conv2d_wgrad_fp32(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
                              int64_t sh, int64_t sw, int64_t ph, int64_t pw,
                              int64_t dh, int64_t dw, int64_t groups);
+
+// classify only: (family, csteps, chunks, accumulate mode) of the launch
+// conv2d_wgrad would make for these operands. Launches nothing.
+std::tuple<std::string, int64_t, int64_t, std::string> conv2d_wgrad_route(
+    at::Tensor gy, at::Tensor x, int64_t R, int64_t S, int64_t sh, int64_t sw,
+    int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t groups) {
+  const WgradRoute r = wgrad_route_of(wgrad_geom(gy, x, groups), R, S, groups);
+  return {wgrad_family_name(r.family), r.csteps, r.chunks,
+          wgrad_acc_name(r.acc)};
+}
 
 at::Tensor conv2d_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
                         int64_t sh, int64_t sw, int64_t ph, int64_t pw,
@@ -963,226 +1009,147 @@ at::Tensor conv2d_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
   CHECK_GPU(gy);
   if (gy.scalar_type() == at::kFloat)
     return conv2d_wgrad_fp32(gy, x, R, S, sh, sw, ph, pw, dh, dw, groups);
-  TORCH_CHECK(gy.scalar_type() == at::kBFloat16, "wgrad: bf16/fp32 only");
-  check_nhwc(gy, "gy");
-  check_nhwc(x, "x");
-  const int N = x.size(0), Ct = x.size(1), H = x.size(2), W = x.size(3);
-  const int Kt = gy.size(1), Ho = gy.size(2), Wo = gy.size(3);
-  const int Cg = Ct / groups, Kg = Kt / groups;
-  TORCH_CHECK(Cg % 8 == 0 && Kg % 8 == 0, "wgrad: Cg/Kg must be multiples of 8");
-  const int64_t M64 = (int64_t)N * Ho * Wo;
-  const bool det = is_deterministic();  // sampled per launch
-  const bool ring_ok = (M64 % 64 == 0) && (Kg % 64 == 0) &&
-                       ((S * Cg) % 64 == 0) && (Cg % 8 == 0) &&
-                       ((R * S * Cg) % 16 == 0);
-  // measured: the ring variant trails the tr-staged kernel on most shapes
-  // (its 8-MFMA k-steps don't cover the pipeline); keep it opt-in.
-  const char* ring_env = getenv("DISTRIBUUUU_WGRAD_RING");
-  const bool ring_on = ring_env && ring_env[0] == '1';
-  if (ring_ok && ring_on) {
-    at::Tensor xin = x;
-    int Hp = H, Wp = W;
-    if (ph > 0 || pw > 0) {
-      Hp = H + 2 * ph;
-      Wp = W + 2 * pw;
-      auto xp = at::empty({(int64_t)N * Hp * Wp * Ct}, x.options());
-      int64_t total = xp.numel();
-      hipLaunchKernelGGL((wg_pad_image_kernel<__hip_bfloat16>),
-                         dim3((Wp * Ct / 8 + 255) / 256, N * Hp), dim3(256),
-                         0, cur_stream(), (const __hip_bfloat16*)x.data_ptr(),
-                         (__hip_bfloat16*)xp.data_ptr(), N, H, W, Ct, Hp, Wp,
-                         ph, pw);
-      xin = xp;
-    }
-    WgradRingParams q;
-    q.x = (const __hip_bfloat16*)xin.data_ptr();
-    q.gy = (const __hip_bfloat16*)gy.data_ptr();
-    q.Hp = Hp; q.Wp = Wp; q.Ct = Ct; q.Kt = Kt;
-    q.R = R; q.S = S; q.Cg = Cg; q.Kg = Kg;
-    q.sh = sh; q.sw = sw; q.dh = dh; q.dw = dw;
-    q.Ho = Ho; q.Wo = Wo;
-    q.M = (int)M64;
-    q.RSC = R * S * Cg;
-    q.ktiles = Kg / WBM;
-    q.ntiles = (q.RSC + WBN - 1) / WBN;
-    const int chunks = (int)((M64 + CHUNK_STEPS * WBK - 1) / (CHUNK_STEPS * WBK));
-    auto accbuf2 = wg_acc_alloc(x, Kt, q.RSC, chunks, det, &q.pstride);
-    q.acc = accbuf2.data_ptr<float>();
-    dim3 grid2(q.ktiles * q.ntiles, chunks, groups);
-    if (det)
-      hipLaunchKernelGGL(conv_wgrad_ring_kernel<true>, grid2, dim3(256), 0,
-                         cur_stream(), q);
-    else
-      hipLaunchKernelGGL(conv_wgrad_ring_kernel<false>, grid2, dim3(256), 0,
-                         cur_stream(), q);
-    return wg_emit_gw(x, accbuf2, Kt, Cg, R, S, chunks, det);
+  const WgradGeom s = wgrad_geom(gy, x, groups);
+  const WgradRoute rt = wgrad_route_of(s, R, S, groups);
+  const int N = s.N, Ct = s.Ct, H = s.H, W = s.W, Kt = s.Kt;
+  const int Ho = s.Ho, Wo = s.Wo, Cg = s.Cg, Kg = s.Kg;
+  const int RSC = R * S * Cg;
+  const bool slab = rt.acc == WgradAcc::Slab;
+  const int chunks = rt.chunks;
+  const unsigned long long magicHoWo =
+      ((1ULL << 47) / ((unsigned long long)Ho * Wo)) + 1;
+  const unsigned long long magicWo = ((1ULL << 47) / (unsigned long long)Wo) + 1;
+  dim3 grid(rt.ktiles * rt.ntiles, chunks, groups);
+
+  // the glds rings read a pre-padded image
+  const bool ringfam = rt.family == WgradFamily::Ring ||
+                       rt.family == WgradFamily::Ring128;
+  at::Tensor xin = x;
+  int Hp = H, Wp = W;
+  if (ringfam && (ph > 0 || pw > 0)) {
+    Hp = H + 2 * ph;
+    Wp = W + 2 * pw;
+    xin = wg_pad_image(x, N, H, W, Ct, ph, pw);
   }
 
-  // 128x128 ring kernel where it measured faster (tools/probes/convmap.py):
-  // 1x1 convolutions (no pad pass, B columns are plain channels) whose
-  // launch has enough tiles+chunks to fill the 256 CUs, and GROUPED deep
-  // 3x3s (RegNetY 232-wide groups: the 64x64 kernel runs out of math to
-  // cover its staging there too — Kg tails are clamped/dropped). Dense 3x3
-  // keeps the 64x64 kernel: pad pass + tap-spanning B columns cost more
-  // than the bigger tile saves.
-  const int64_t blocks64 = (((int64_t)Kg + 127) / 128) *
-                           (((int64_t)R * S * Cg + 127) / 128) *
-                           ((M64 + CHUNK_STEPS * WBK - 1) / (CHUNK_STEPS * WBK));
-  const bool dense1x1 = R == 1 && S == 1 && Kg % 128 == 0 && Cg >= 128;
-  // M >= 8192: measured crossover (tools/probes/wgrad_group_ab.py) — the
-  // 7x7 grouped shapes stay on the 64x64 kernel (85 vs 118 us)
-  const bool grouped_deep = groups > 1 && Kg >= 96 &&
-                            (int64_t)R * S * Cg >= 512 && M64 >= 8192;
-  // DISTRIBUUUU_WGRAD_128: 1 forces the ring128 route (A/B probes, tests of
-  // the Kg-tail path on small shapes), 0 disables it; re-read per call
-  const char* f128 = getenv("DISTRIBUUUU_WGRAD_128");
-  const int force128 = f128 ? atoi(f128) : -1;
-  const bool gate_ok = (dense1x1 || grouped_deep) &&
-                       blocks64 * groups >= 320;
-  if (force128 != 0 && M64 % 64 == 0 && Cg % 8 == 0 &&
-      (gate_ok || force128 == 1)) {
-    at::Tensor xin = x;
-    int Hp = H, Wp = W;
-    if (ph > 0 || pw > 0) {
-      Hp = H + 2 * ph;
-      Wp = W + 2 * pw;
-      auto xp = at::empty({(int64_t)N * Hp * Wp * Ct}, x.options());
-      int64_t total = xp.numel();
-      hipLaunchKernelGGL((wg_pad_image_kernel<__hip_bfloat16>),
-                         dim3((Wp * Ct / 8 + 255) / 256, N * Hp), dim3(256),
-                         0, cur_stream(), (const __hip_bfloat16*)x.data_ptr(),
-                         (__hip_bfloat16*)xp.data_ptr(), N, H, W, Ct, Hp, Wp,
-                         ph, pw);
-      xin = xp;
-    }
-    Wgrad128Params q;
-    q.x = (const __hip_bfloat16*)xin.data_ptr();
-    q.gy = (const __hip_bfloat16*)gy.data_ptr();
-    q.Hp = Hp; q.Wp = Wp; q.Ct = Ct; q.Kt = Kt;
-    q.R = R; q.S = S; q.Cg = Cg; q.Kg = Kg;
-    q.sh = sh; q.sw = sw; q.dh = dh; q.dw = dw;
-    q.Ho = Ho; q.Wo = Wo;
-    q.M = (int)M64;
-    q.RSC = R * S * Cg;
-    q.ktiles = (Kg + R128_BM - 1) / R128_BM;
-    q.ntiles = (q.RSC + R128_BN - 1) / R128_BN;
-    q.magicHoWo = ((1ULL << 47) / ((unsigned long long)Ho * Wo)) + 1;
-    q.magicWo = ((1ULL << 47) / (unsigned long long)Wo) + 1;
-    // shrink the split-m chunk until the launch fills the 256 CUs
-    int csteps = CHUNK_STEPS;
-    int chunks = (int)((M64 + (int64_t)csteps * WBK - 1) / (csteps * WBK));
-    while (csteps > 8 && (int64_t)q.ktiles * q.ntiles * chunks * groups < 512) {
-      csteps /= 2;
-      chunks = (int)((M64 + (int64_t)csteps * WBK - 1) / (csteps * WBK));
-    }
-    if (det) {  // bound the workspace (DET_WS_CAP)
-      csteps = det_grow_csteps(csteps, M64, (int64_t)Kt * q.RSC);
-      chunks = (int)((M64 + (int64_t)csteps * WBK - 1) / (csteps * WBK));
-    }
-    q.csteps = csteps;
-    auto accbuf = wg_acc_alloc(x, Kt, q.RSC, chunks, det, &q.pstride);
-    q.acc = accbuf.data_ptr<float>();
-    static bool attr_done = false;
-    if (!attr_done) {
-      hipFuncSetAttribute((const void*)conv_wgrad_ring128_kernel<false>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize,
-                          3 * R128_SLOT);
-      hipFuncSetAttribute((const void*)conv_wgrad_ring128_kernel<true>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize,
-                          3 * R128_SLOT);
-      attr_done = true;
-    }
-    dim3 grid(q.ktiles * q.ntiles, chunks, groups);
-    if (det)
-      hipLaunchKernelGGL(conv_wgrad_ring128_kernel<true>, grid, dim3(256),
-                         3 * R128_SLOT, cur_stream(), q);
-    else
-      hipLaunchKernelGGL(conv_wgrad_ring128_kernel<false>, grid, dim3(256),
-                         3 * R128_SLOT, cur_stream(), q);
-    return wg_emit_gw(x, accbuf, Kt, Cg, R, S, chunks, det);
-  }
+  int64_t pstride;
+  auto acc = wg_acc_alloc(x, Kt, RSC, chunks, slab, &pstride);
 
-  // 128x128 tr-staged tile (A/B via DISTRIBUUUU_WGRAD_T128: 1 force,
-  // 0 off, default auto-gate from the probe measurements)
-  {
-    const char* e = getenv("DISTRIBUUUU_WGRAD_T128");
-    const int t128 = e ? atoi(e) : -1;
-    const int64_t t128_blocks =
-        (int64_t)((Kg + 127) / 128) * (((int64_t)R * S * Cg + 127) / 128) *
-        ((M64 + CHUNK_STEPS * WBK - 1) / (CHUNK_STEPS * WBK)) * groups;
-    // measured (tools/probes/wgrad_dense_ab.py): wins/ties every dense 3x3
-    // with Kg >= 128 (512-deep: -13%), loses at Kg = 64 (half-empty tiles)
-    const bool t128_gate = Kg >= 128 && (int64_t)R * S * Cg >= 128;
-    if (t128 == 1 || (t128 == -1 && t128_gate)) {
+  switch (rt.family) {
+    case WgradFamily::Ring: {
+      WgradRingParams q;
+      q.x = (const __hip_bfloat16*)xin.data_ptr();
+      q.gy = (const __hip_bfloat16*)gy.data_ptr();
+      q.acc = acc.data_ptr<float>();
+      q.Hp = Hp; q.Wp = Wp; q.Ct = Ct; q.Kt = Kt;
+      q.R = R; q.S = S; q.Cg = Cg; q.Kg = Kg;
+      q.sh = sh; q.sw = sw; q.dh = dh; q.dw = dw;
+      q.Ho = Ho; q.Wo = Wo;
+      q.M = (int)s.M;
+      q.RSC = RSC;
+      q.ktiles = rt.ktiles;
+      q.ntiles = rt.ntiles;
+      q.pstride = pstride;
+      if (slab)
+        hipLaunchKernelGGL(conv_wgrad_ring_kernel<true>, grid, dim3(256), 0,
+                           cur_stream(), q);
+      else
+        hipLaunchKernelGGL(conv_wgrad_ring_kernel<false>, grid, dim3(256), 0,
+                           cur_stream(), q);
+      break;
+    }
+    case WgradFamily::Ring128: {
+      Wgrad128Params q;
+      q.x = (const __hip_bfloat16*)xin.data_ptr();
+      q.gy = (const __hip_bfloat16*)gy.data_ptr();
+      q.acc = acc.data_ptr<float>();
+      q.Hp = Hp; q.Wp = Wp; q.Ct = Ct; q.Kt = Kt;
+      q.R = R; q.S = S; q.Cg = Cg; q.Kg = Kg;
+      q.sh = sh; q.sw = sw; q.dh = dh; q.dw = dw;
+      q.Ho = Ho; q.Wo = Wo;
+      q.M = (int)s.M;
+      q.RSC = RSC;
+      q.ktiles = rt.ktiles;
+      q.ntiles = rt.ntiles;
+      q.csteps = rt.csteps;
+      q.magicHoWo = magicHoWo;
+      q.magicWo = magicWo;
+      q.pstride = pstride;
+      static bool attr_done = false;
+      if (!attr_done) {
+        hipFuncSetAttribute((const void*)conv_wgrad_ring128_kernel<false>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            3 * R128_SLOT);
+        hipFuncSetAttribute((const void*)conv_wgrad_ring128_kernel<true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            3 * R128_SLOT);
+        attr_done = true;
+      }
+      if (slab)
+        hipLaunchKernelGGL(conv_wgrad_ring128_kernel<true>, grid, dim3(256),
+                           3 * R128_SLOT, cur_stream(), q);
+      else
+        hipLaunchKernelGGL(conv_wgrad_ring128_kernel<false>, grid, dim3(256),
+                           3 * R128_SLOT, cur_stream(), q);
+      break;
+    }
+    case WgradFamily::Tr128: {
       WgradT128Params q;
       q.x = (const __hip_bfloat16*)x.data_ptr();
       q.gy = (const __hip_bfloat16*)gy.data_ptr();
+      q.acc = acc.data_ptr<float>();
       q.N = N; q.H = H; q.W = W; q.Ct = Ct; q.Kt = Kt;
       q.R = R; q.S = S; q.Cg = Cg; q.Kg = Kg;
       q.sh = sh; q.sw = sw; q.ph = ph; q.pw = pw; q.dh = dh; q.dw = dw;
       q.Ho = Ho; q.Wo = Wo;
-      q.M = (int)M64;
-      q.RSC = R * S * Cg;
-      q.ktiles = (Kg + T128_BM - 1) / T128_BM;
-      q.ntiles = (q.RSC + T128_BN - 1) / T128_BN;
+      q.M = (int)s.M;
+      q.RSC = RSC;
+      q.ktiles = rt.ktiles;
+      q.ntiles = rt.ntiles;
+      q.chunks = chunks;
+      q.csteps = rt.csteps;
       {
         const char* xr = getenv("DISTRIBUUUU_WGRAD_XCD");
         q.xcd_remap = xr && xr[0] == '0' ? 0 : 1;
       }
-      q.magicHoWo = ((1ULL << 47) / ((unsigned long long)Ho * Wo)) + 1;
-      q.magicWo = ((1ULL << 47) / (unsigned long long)Wo) + 1;
-      int csteps = CHUNK_STEPS;
-      int chunks = (int)((M64 + (int64_t)csteps * WBK - 1) / (csteps * WBK));
-      while (csteps > 8 &&
-             (int64_t)q.ktiles * q.ntiles * chunks * groups < 512) {
-        csteps /= 2;
-        chunks = (int)((M64 + (int64_t)csteps * WBK - 1) / (csteps * WBK));
-      }
-      if (det) {  // bound the workspace (DET_WS_CAP)
-        csteps = det_grow_csteps(csteps, M64, (int64_t)Kt * q.RSC);
-        chunks = (int)((M64 + (int64_t)csteps * WBK - 1) / (csteps * WBK));
-      }
-      q.csteps = csteps;
-      q.chunks = chunks;
-      auto accb = wg_acc_alloc(x, Kt, q.RSC, chunks, det, &q.pstride);
-      q.acc = accb.data_ptr<float>();
-      dim3 grid(q.ktiles * q.ntiles, chunks, groups);
-      if (det)
+      q.magicHoWo = magicHoWo;
+      q.magicWo = magicWo;
+      q.pstride = pstride;
+      if (slab)
         hipLaunchKernelGGL(conv_wgrad_tr128_kernel<true>, grid, dim3(256), 0,
                            cur_stream(), q);
       else
         hipLaunchKernelGGL(conv_wgrad_tr128_kernel<false>, grid, dim3(256), 0,
                            cur_stream(), q);
-      return wg_emit_gw(x, accb, Kt, Cg, R, S, chunks, det);
+      break;
     }
-    (void)t128_blocks;
+    case WgradFamily::T64: {
+      WgradParams p;
+      p.x = (const __hip_bfloat16*)x.data_ptr();
+      p.gy = (const __hip_bfloat16*)gy.data_ptr();
+      p.acc = acc.data_ptr<float>();
+      p.N = N; p.H = H; p.W = W; p.Ct = Ct; p.Kt = Kt;
+      p.R = R; p.S = S; p.Cg = Cg; p.Kg = Kg;
+      p.sh = sh; p.sw = sw; p.ph = ph; p.pw = pw; p.dh = dh; p.dw = dw;
+      p.Ho = Ho; p.Wo = Wo;
+      p.M = (int)s.M;
+      p.RSC = RSC;
+      p.ktiles = rt.ktiles;
+      p.ntiles = rt.ntiles;
+      p.chunks = chunks;
+      p.magicHoWo = magicHoWo;
+      p.magicWo = magicWo;
+      p.pstride = pstride;
+      if (p.ktiles * p.ntiles <= 12)  // XCD-grouped 1-D grid (see kernel)
+        grid = dim3(p.ktiles * p.ntiles * ((chunks + 7) / 8 * 8), 1, groups);
+      if (slab)
+        hipLaunchKernelGGL(conv_wgrad_kernel<true>, grid, dim3(256), 0,
+                           cur_stream(), p);
+      else
+        hipLaunchKernelGGL(conv_wgrad_kernel<false>, grid, dim3(256), 0,
+                           cur_stream(), p);
+      break;
+    }
   }
-
-  WgradParams p;
-  p.x = (const __hip_bfloat16*)x.data_ptr();
-  p.gy = (const __hip_bfloat16*)gy.data_ptr();
-  p.N = N; p.H = H; p.W = W; p.Ct = Ct; p.Kt = Kt;
-  p.R = R; p.S = S; p.Cg = Cg; p.Kg = Kg;
-  p.sh = sh; p.sw = sw; p.ph = ph; p.pw = pw; p.dh = dh; p.dw = dw;
-  p.Ho = Ho; p.Wo = Wo;
-  p.M = N * Ho * Wo;
-  p.RSC = R * S * Cg;
-  p.ktiles = (Kg + WBM - 1) / WBM;
-  p.ntiles = (p.RSC + WBN - 1) / WBN;
-  p.chunks = (p.M + CHUNK_STEPS * WBK - 1) / (CHUNK_STEPS * WBK);
-  p.magicHoWo = ((1ULL << 47) / ((unsigned long long)Ho * Wo)) + 1;
-  p.magicWo = ((1ULL << 47) / (unsigned long long)Wo) + 1;
-
-  auto accbuf = wg_acc_alloc(x, Kt, p.RSC, p.chunks, det, &p.pstride);
-  p.acc = accbuf.data_ptr<float>();
-  dim3 grid(p.ktiles * p.ntiles, p.chunks, groups);
-  if (p.ktiles * p.ntiles <= 12)  // XCD-grouped 1-D grid (see kernel)
-    grid = dim3(p.ktiles * p.ntiles * ((p.chunks + 7) / 8 * 8), 1, groups);
-  if (det)
-    hipLaunchKernelGGL(conv_wgrad_kernel<true>, grid, dim3(256), 0,
-                       cur_stream(), p);
-  else
-    hipLaunchKernelGGL(conv_wgrad_kernel<false>, grid, dim3(256), 0,
-                       cur_stream(), p);
-  return wg_emit_gw(x, accbuf, Kt, Cg, R, S, p.chunks, det);
+  return wg_emit_gw(x, acc, Kt, Cg, R, S, chunks, slab);
 }

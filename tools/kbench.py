@@ -5,6 +5,10 @@ Groups: bn conv wgrad pool fused gemm sgd mix all
 Prints achieved GB/s (memory-bound ops) or TF/s (MFMA ops) per shape.
 --deterministic: the wgrad rows time each shape in both modes, atomic and
 deterministic (docs/DETERMINISM.md), side by side.
+Without it the wgrad group ends with the accumulate-mode table: every distinct
+ResNet-50 wgrad launch under DISTRIBUUUU_WGRAD_ACC=atomic and =slab, alternated
+over three passes; --slab-blocks=256,384 adds slab columns with another
+block-count target (DISTRIBUUUU_WGRAD_SLAB_BLOCKS).
 """
 
 import sys
@@ -119,7 +123,7 @@ def _bench_halo_routes(x, wt, flops, passes=3):
             print(row)
 
 
-def bench_wgrad(deterministic=False):
+def bench_wgrad(deterministic=False, slab_blocks=()):
     from distribuuuu_amd import ops
 
     print("== conv wgrad (TF/s) ==" if not deterministic else
@@ -144,6 +148,87 @@ def bench_wgrad(deterministic=False):
             line += (f" | det {td*1e6:8.1f} us {flops/td/1e12:6.1f} TF"
                      f"  x{td/t:4.2f}")
         print(line)
+    if not deterministic:
+        _bench_wgrad_acc(slab_blocks)
+
+
+def _resnet50_wgrad_shapes(n=256):
+    """ResNet-50's distinct weight-gradient launches at batch n, in network
+    order: ((N, C, H, W, K, R, stride, pad), calls per step). The stem sees
+    its input zero-padded to 8 channels."""
+    shapes = {(n, 8, 224, 224, 64, 7, 2, 3): 1}
+    cin, h = 64, 56
+    for width, blocks, stride in ((64, 3, 1), (128, 4, 2), (256, 6, 2),
+                                  (512, 3, 2)):
+        for b in range(blocks):
+            st = stride if b == 0 else 1
+            convs = [(n, cin, h, h, width, 1, 1, 0),
+                     (n, width, h, h, width, 3, st, 1),
+                     (n, width, h // st, h // st, 4 * width, 1, 1, 0)]
+            if b == 0:
+                convs.append((n, cin, h, h, 4 * width, 1, st, 0))
+            for c in convs:
+                shapes[c] = shapes.get(c, 0) + 1
+            cin, h = 4 * width, h // st
+    return list(shapes.items())
+
+
+def _bench_wgrad_acc(slab_blocks=(), passes=3):
+    """Accumulate modes of the split-m wgrad (DISTRIBUUUU_WGRAD_ACC), forced
+    through the knob and alternated over `passes` passes per shape. Op time is
+    the whole conv2d_wgrad call: accumulator setup (memset or nothing), the
+    wgrad kernel, and the cast or the ordered reduction. `auto` is what the
+    classifier picks at default gates; extra `slab@B` columns run slab with
+    the csteps shrink loop aiming at B blocks instead of 512."""
+    import os
+
+    print("== conv wgrad accumulate modes, ResNet-50 batch 256 (us; family "
+          "csteps x chunks; slot = Kt*RSC*4) ==")
+    cols = [("atomic", {"DISTRIBUUUU_WGRAD_ACC": "atomic"}),
+            ("slab", {"DISTRIBUUUU_WGRAD_ACC": "slab"})]
+    for b in slab_blocks:
+        cols.append((f"slab@{b}", {"DISTRIBUUUU_WGRAD_ACC": "slab",
+                                   "DISTRIBUUUU_WGRAD_SLAB_BLOCKS": str(b)}))
+    knobs = ("DISTRIBUUUU_WGRAD_ACC", "DISTRIBUUUU_WGRAD_SLAB_BLOCKS")
+    saved = {k: os.environ.pop(k, None) for k in knobs}
+
+    def with_env(env, fn):
+        for k in knobs:
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        try:
+            return fn()
+        finally:
+            for k in knobs:
+                os.environ.pop(k, None)
+
+    try:
+        for shp, calls in _resnet50_wgrad_shapes():
+            n, c, h, w, k, r, s, p = shp
+            x = _cl(torch.randn(n, c, h, w, device=DEV, dtype=torch.bfloat16))
+            ho = (h + 2 * p - r) // s + 1
+            gy = _cl(torch.randn(n, k, ho, ho, device=DEV,
+                                 dtype=torch.bfloat16))
+            args = (gy, x, r, r, s, s, p, p, 1, 1, 1)
+            route = lambda: e.conv2d_wgrad_route(*args)
+            auto = with_env({}, route)
+            head = f"{str(shp):38s} x{calls} slot {k*r*r*c*4/1024:7.0f} KB"
+            for label, env in cols:
+                fam, cs, ch, acc = with_env(env, route)
+                head += f" | {label} {fam} {cs}x{ch} {acc}"
+            print(head + f" | auto -> {auto[3]}")
+            for i in range(passes):
+                row = f"  pass {i}"
+                for label, env in cols:
+                    t = with_env(env, lambda: timeit(
+                        lambda: e.conv2d_wgrad(*args)))
+                    row += f" | {label} {t*1e6:7.1f}"
+                print(row)
+            del x, gy
+    finally:
+        for k, v in saved.items():
+            if v is not None:
+                os.environ[k] = v
 
 
 def bench_pool():
@@ -305,13 +390,17 @@ def bench_mix(passes=3):
 if __name__ == "__main__":
     args = sys.argv[1:]
     deterministic = "--deterministic" in args
-    groups = [a for a in args if a != "--deterministic"] or ["all"]
+    slab_blocks = ()
+    for a in args:
+        if a.startswith("--slab-blocks="):
+            slab_blocks = tuple(int(v) for v in a.split("=")[1].split(","))
+    groups = [a for a in args if not a.startswith("--")] or ["all"]
     if "bn" in groups or "all" in groups:
         bench_bn()
     if "conv" in groups or "all" in groups:
         bench_conv()
     if "wgrad" in groups or "all" in groups:
-        bench_wgrad(deterministic)
+        bench_wgrad(deterministic, slab_blocks)
     if "pool" in groups or "all" in groups:
         bench_pool()
     if "fused" in groups or "all" in groups:
