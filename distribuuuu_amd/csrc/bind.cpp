@@ -58,13 +58,6 @@ std::vector<at::Tensor> bn_pool_bwd(at::Tensor gpool, at::Tensor idx,
                                     at::Tensor rstd, at::Tensor gamma,
                                     at::Tensor scale, at::Tensor shift,
                                     int64_t act, bool training);
-at::Tensor bn_apply_act_pad(at::Tensor x, at::Tensor scale, at::Tensor shift,
-                            int64_t act, int64_t ph, int64_t pw);
-std::vector<at::Tensor> bn_bwd_pad(at::Tensor gy, at::Tensor x,
-                                   at::Tensor mean, at::Tensor rstd,
-                                   at::Tensor gamma, at::Tensor scale,
-                                   at::Tensor shift, int64_t act,
-                                   bool training, int64_t ph, int64_t pw);
 // pool.hip
 std::vector<at::Tensor> maxpool_fwd(at::Tensor x, int64_t K, int64_t S,
                                     int64_t P);
@@ -112,13 +105,6 @@ std::tuple<std::string, int64_t, bool> conv2d_dgrad_route(
     at::Tensor gy, at::Tensor w, int64_t H, int64_t W, int64_t sh, int64_t sw,
     int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t groups,
     c10::optional<at::Tensor> into);
-std::vector<at::Tensor> conv2d_dgrad_bn(at::Tensor gy, at::Tensor w,
-                                        int64_t H, int64_t W, int64_t sh,
-                                        int64_t sw, int64_t ph, int64_t pw,
-                                        int64_t dh, int64_t dw,
-                                        int64_t groups, at::Tensor bnx,
-                                        at::Tensor bnscale, at::Tensor bnshift,
-                                        int64_t bnact);
 
 std::tuple<at::Tensor, int64_t> conv2d_dgrad_acc(
     at::Tensor gy, at::Tensor w, int64_t H, int64_t W, int64_t sh, int64_t sw,
@@ -207,8 +193,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_pool_bwd_stats", &bn_pool_bwd_stats);
   m.def("bn_pool_bwd_apply", &bn_pool_bwd_apply);
   m.def("bn_pool_bwd", &bn_pool_bwd);
-  m.def("bn_apply_act_pad", &bn_apply_act_pad);
-  m.def("bn_bwd_pad", &bn_bwd_pad);
   m.def("bn_bwd_stats", &bn_bwd_stats, py::arg("gy"), py::arg("x"),
         py::arg("res"), py::arg("scale"), py::arg("shift"),
         py::arg("act"));
@@ -258,7 +242,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w"), py::arg("H"), py::arg("W"), py::arg("sh"),
         py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("dh"),
         py::arg("dw"), py::arg("groups"), py::arg("into") = py::none());
-  m.def("conv2d_dgrad_bn", &conv2d_dgrad_bn);
   m.def("conv2d_dgrad_acc", &conv2d_dgrad_acc);
   m.def("conv2d_dgrad_prep", &conv2d_dgrad_prep);
   m.def("conv2d_wgrad", &conv2d_wgrad);

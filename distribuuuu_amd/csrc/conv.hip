@@ -43,22 +43,13 @@ struct ConvParams {
   int M, nspan, ksteps;     // nspan = ceil(S*Cg/BK), ksteps = R*nspan
   int tiles_m;              // for XCD swizzle
   float* part;              // EMIT: [tiles_m*2, 2*Kt] BN sum/sumsq partials
-  // EMODE 2 (dgrad -> BN-backward stats): this conv's output IS the
-  // consuming BatchNorm's upstream grad gy; the epilogue also reads the
-  // BN's input x at the SAME positions and emits [sum(g), sum(g*x)]
-  // partials with g = act'(x*scale+shift) * gy — the standalone
-  // bn_bwd_reduce pass over the whole tensor disappears.
-  const __hip_bfloat16* bnx;
-  const float* bnscale;
-  const float* bnshift;
-  int bnact;                // 0 none, 1 relu
 };
 
-// EMODE: 0 plain, 1 forward BN sum/sumsq partials, 2 backward masked stats.
+// EMIT: epilogue also writes the forward BN sum/sumsq partials.
 // ACC: epilogue accumulates into y (residual-fork dgrad into gres).
-template <int EMODE, bool ACC = false>
+template <bool EMIT, bool ACC = false>
 __global__ __launch_bounds__(256) void conv_igemm_fwd_kernel(ConvParams p) {
-  static_assert(!(ACC && EMODE != 0), "ACC only with plain epilogue");
+  static_assert(!(ACC && EMIT), "ACC only with plain epilogue");
   const int g = blockIdx.z;
   // XCD-aware swizzle over m-tiles (T1; bijective form)
   int tile_m = blockIdx.x, tile_n = blockIdx.y;
@@ -241,68 +232,14 @@ __global__ __launch_bounds__(256) void conv_igemm_fwd_kernel(ConvParams p) {
           if (k0 + j < p.Kg) p.y[obase + k0 + j] = u.b[j];
       }
     }
-    if (EMODE == 1) {
+    if (EMIT) {
       const int base = tile_m * BM + wm * 64 + mi * 16;
       bn_partial_col_accum(slab, ps, pq,
                            (int)min((int64_t)16, (int64_t)p.M - base), lane);
     }
-    if (EMODE == 2) {
-      // load x at the SAME positions, build g = act'(x*scale+shift)*gy,
-      // run the two-pass slab column accumulation (g, then g*x)
-      union {
-        __hip_bfloat16 b[16];
-        uint4 q[2];
-      } xv;
-      const int k0 = tile_n * BN + wn * 64 + ec;
-      bool valid = m < p.M;
-      if (valid) {
-        const int n = m / HoWo;
-        const int rem = m - n * HoWo;
-        const int64_t obase =
-            (((int64_t)n * p.HoA + (rem / p.Wo) * p.osh + p.oh0) * p.WoA +
-             (rem % p.Wo) * p.osw + p.ow0) * p.Kt + g * p.Kg;
-        if (k0 + 16 <= p.Kg) {
-          xv.q[0] = *reinterpret_cast<const uint4*>(&p.bnx[obase + k0]);
-          xv.q[1] = *reinterpret_cast<const uint4*>(&p.bnx[obase + k0 + 8]);
-        } else {
-          xv.q[0] = uint4{0, 0, 0, 0};
-          xv.q[1] = uint4{0, 0, 0, 0};
-#pragma unroll
-          for (int j = 0; j < 16; ++j)
-            if (k0 + j < p.Kg) xv.b[j] = p.bnx[obase + k0 + j];
-        }
-      }
-      __builtin_amdgcn_wave_barrier();  // everyone done with the y stripe
-      // pass 1: g   (invalid rows contribute zeros)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        float gj = 0.f;
-        if (valid) {
-          const int cc = g * p.Kg + k0 + j;
-          const float yj = to_f32(from_f32<__hip_bfloat16>(
-              slab[er * 68 + ec + j]));  // the ROUNDED stored gy
-          gj = yj;
-          if (p.bnact == 1 &&
-              to_f32(xv.b[j]) * p.bnscale[cc] + p.bnshift[cc] <= 0.f)
-            gj = 0.f;
-        }
-        slab[er * 68 + ec + j] = gj;
-      }
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ps += slab[r * 68 + lane];
-      __builtin_amdgcn_wave_barrier();
-      // pass 2: g*x (read own g back, multiply by x)
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        slab[er * 68 + ec + j] *= valid ? to_f32(xv.b[j]) : 0.f;
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int r = 0; r < 16; ++r) pq += slab[r * 68 + lane];
-    }
     __builtin_amdgcn_wave_barrier();
   }
-  if (EMODE == 1 || EMODE == 2) {
+  if (EMIT) {
     // cross-wave (wm) combine via LDS halves the partial rows
     float* xarea = reinterpret_cast<float*>(&ldsB[0][0][0]);
     if (wm == 1) {
@@ -836,14 +773,13 @@ __global__ __launch_bounds__(256) void conv_smallk_pipe_kernel(
 // host wrappers
 // ---------------------------------------------------------------------------
 // one launch per kernel family: each picks the instantiation from its flags
-static void launch_v1(const ConvParams& p, dim3 grid, int emode, bool acc) {
+static void launch_v1(const ConvParams& p, dim3 grid, bool emit, bool acc) {
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, cur_stream(), p);
   };
-  if (emode == 2) go(conv_igemm_fwd_kernel<2>);
-  else if (emode == 1) go(conv_igemm_fwd_kernel<1>);
-  else if (acc) go(conv_igemm_fwd_kernel<0, true>);
-  else go(conv_igemm_fwd_kernel<0>);
+  if (emit) go(conv_igemm_fwd_kernel<true>);
+  else if (acc) go(conv_igemm_fwd_kernel<false, true>);
+  else go(conv_igemm_fwd_kernel<false>);
 }
 
 // small 1x1 GEMM family: the register-cached C = 64 / 32 kernels, else generic
@@ -873,13 +809,11 @@ at::Tensor conv2d_fwd_into(at::Tensor x, at::Tensor w, at::Tensor y, int64_t Ho,
                            int64_t pw, int64_t dh, int64_t dw, int64_t groups,
                            int64_t osh = 1, int64_t osw = 1, int64_t oh0 = 0,
                            int64_t ow0 = 0, at::Tensor* part_out = nullptr,
-                           const BnBwdEmit* bemit = nullptr,
                            bool acc = false) {
   CHECK_GPU(x);
   if (x.scalar_type() == at::kFloat)
     return conv2d_fwd_into_fp32(x, w, y, Ho, Wo, sh, sw, ph, pw, dh, dw,
-                                groups, osh, osw, oh0, ow0,
-                                bemit ? nullptr : part_out);
+                                groups, osh, osw, oh0, ow0, part_out);
   TORCH_CHECK(x.scalar_type() == at::kBFloat16, "conv2d_fwd: bf16/fp32 only");
   {
     // deep pad-free windows (parity-decomposed / strided dgrads) ride the
@@ -887,8 +821,8 @@ at::Tensor conv2d_fwd_into(at::Tensor x, at::Tensor w, at::Tensor y, int64_t Ho,
     const ConvGates& gates = conv_gates();
     const int Cgi = w.size(1), Ri = w.size(2), Si = w.size(3);
     const int Kgi = (int)(w.size(0) / groups);
-    if (gates.v2into && part_out == nullptr && bemit == nullptr && ph == 0 &&
-        pw == 0 && sh == 1 && sw == 1 && dh == 1 && dw == 1 &&
+    if (gates.v2into && part_out == nullptr && ph == 0 && pw == 0 &&
+        sh == 1 && sw == 1 && dh == 1 && dw == 1 &&
         (Si * Cgi) % 64 == 0 && Kgi >= 96 &&
         (int64_t)Ri * Si * Cgi >= gates.v2into_minrsc && Cgi % 8 == 0 &&
         Ho + Ri - 1 <= x.size(2) && Wo + Si - 1 <= x.size(3))
@@ -918,24 +852,13 @@ at::Tensor conv2d_fwd_into(at::Tensor x, at::Tensor w, at::Tensor y, int64_t Ho,
   p.ksteps = R * p.nspan;
   p.tiles_m = (p.M + BM - 1) / BM;
   p.part = nullptr;
-  p.bnx = nullptr;
-  p.bnscale = nullptr;
-  p.bnshift = nullptr;
-  p.bnact = 0;
   dim3 grid(p.tiles_m, (Kg + BN - 1) / BN, groups);
-  const int emode = bemit != nullptr ? 2 : part_out != nullptr ? 1 : 0;
-  if (emode != 0) {
+  if (part_out != nullptr) {
     *part_out = at::empty({(int64_t)p.tiles_m, (int64_t)2 * Kt},
                           x.options().dtype(at::kFloat));
     p.part = part_out->data_ptr<float>();
   }
-  if (bemit != nullptr) {
-    p.bnx = bemit->x;
-    p.bnscale = bemit->scale;
-    p.bnshift = bemit->shift;
-    p.bnact = bemit->act;
-  }
-  launch_v1(p, grid, emode, acc);
+  launch_v1(p, grid, part_out != nullptr, acc);
   return y;
 }
 
@@ -945,7 +868,6 @@ static at::Tensor conv2d_fwd_impl(at::Tensor x, at::Tensor w, int64_t sh,
                                   int64_t sw, int64_t ph, int64_t pw,
                                   int64_t dh, int64_t dw, int64_t groups,
                                   at::Tensor* part_out,
-                                  const BnBwdEmit* bemit = nullptr,
                                   int halo_force = -1) {
   const int N = x.size(0), H = x.size(2), W = x.size(3);
   const int Kt = w.size(0), R = w.size(2), S = w.size(3);
@@ -956,8 +878,7 @@ static at::Tensor conv2d_fwd_impl(at::Tensor x, at::Tensor w, int64_t sh,
   // per-group geometry decides the ring gate (v2_ring_ok)
   if (v2_ring_ok(Kt / (int)groups, C_ / (int)groups, R, S,
                  x.scalar_type() == at::kBFloat16))
-    return conv2d_fwd_v2p(x, w, sh, sw, ph, pw, dh, dw, groups, part_out,
-                          bemit);
+    return conv2d_fwd_v2p(x, w, sh, sw, ph, pw, dh, dw, groups, part_out);
   if (gates.small && groups == 1 && R == 1 && S == 1 && sh == 1 && sw == 1 &&
       C_ % 32 == 0 && Kt % 64 == 0 && x.scalar_type() == at::kBFloat16 &&
       ((C_ <= 64 && Kt <= 512) || (C_ <= 256 && Kt <= 64))) {
@@ -971,7 +892,6 @@ static at::Tensor conv2d_fwd_impl(at::Tensor x, at::Tensor w, int64_t sh,
     sp.C = C_; sp.Kt = Kt; sp.M = M;
     sp.part = nullptr;
     const dim3 sg((int)((M + 255) / 256));
-    if (bemit != nullptr) part_out = nullptr;  // small 1x1: no bwd emission
     if (part_out != nullptr) {
       *part_out = at::empty({(int64_t)sg.x, (int64_t)2 * Kt},
                             x.options().dtype(at::kFloat));
@@ -1016,7 +936,6 @@ static at::Tensor conv2d_fwd_impl(at::Tensor x, at::Tensor w, int64_t sh,
     sp.zbuf = (const __hip_bfloat16*)zbuf.data_ptr();
     sp.part = nullptr;
     const dim3 skg((int)((sp.M + 255) / 256));
-    if (bemit != nullptr) part_out = nullptr;  // smallk: no bwd emission
     // 3x3 / stride 1 / pad 1 / 64->64: input tile + halo staged in LDS once
     // instead of nine global reads per pixel (conv_halo.hip); bit-identical
     const bool halo_fits =
@@ -1047,7 +966,7 @@ static at::Tensor conv2d_fwd_impl(at::Tensor x, at::Tensor w, int64_t sh,
   auto y = at::empty({N, Kt, Ho, Wo},
                      x.options().memory_format(at::MemoryFormat::ChannelsLast));
   return conv2d_fwd_into(x, w, y, Ho, Wo, sh, sw, ph, pw, dh, dw, groups, 1,
-                         1, 0, 0, part_out, bemit);
+                         1, 0, 0, part_out);
 }
 
 
@@ -1073,7 +992,7 @@ std::vector<at::Tensor> conv2d_fwd_halo_dbg(at::Tensor x, at::Tensor w,
                                             bool emit, bool halo) {
   at::Tensor part;
   auto y = conv2d_fwd_impl(x, w, 1, 1, 1, 1, 1, 1, 1, emit ? &part : nullptr,
-                           nullptr, halo ? 1 : 0);
+                           halo ? 1 : 0);
   if (!emit) return {y};
   TORCH_CHECK(part.defined(), "conv2d_fwd_halo_dbg: route without partials");
   return {y, part};
@@ -1311,16 +1230,13 @@ static at::Tensor conv2d_dgrad_run(DgradRoute rt, at::Tensor gy, at::Tensor w,
                                    int64_t H, int64_t W, int64_t sh,
                                    int64_t sw, int64_t ph, int64_t pw,
                                    int64_t dh, int64_t dw, int64_t groups,
-                                   at::Tensor* part_out,
-                                   const BnBwdEmit* bemit,
                                    const at::Tensor* pre = nullptr,
                                    int64_t pre_kind = -1,
                                    at::Tensor* into = nullptr) {
   CHECK_GPU(gy);
   check_nhwc(gy, "gy");
   const bool acc = rt.acc;
-  TORCH_CHECK(!acc || (into && !part_out && !bemit),
-              "dgrad: acc needs a buffer and excludes partial emission");
+  TORCH_CHECK(!acc || into, "dgrad: acc needs a buffer");
   const int N = gy.size(0);
   const int Cg = w.size(1), R = w.size(2), S = w.size(3);
   const int Ct = Cg * groups;
@@ -1338,7 +1254,7 @@ static at::Tensor conv2d_dgrad_run(DgradRoute rt, at::Tensor gy, at::Tensor w,
                    ? *pre
                    : weight_flip_t_span(w, groups, SPAN64);
     return conv2d_fwd_v2_flat(gy, wsp, Ct, fCg, R, S, 1, 1, pph, ppw, dh, dw,
-                              groups, part_out, bemit, acc ? into : nullptr);
+                              groups, nullptr, acc ? into : nullptr);
   }
   auto wt = (pre != nullptr && pre_kind == 0)
                 ? *pre
@@ -1346,14 +1262,12 @@ static at::Tensor conv2d_dgrad_run(DgradRoute rt, at::Tensor gy, at::Tensor w,
   switch (rt.kind) {
     case DgradKind::Strided1x1: {
       // strided-output GEMM: gx[ho*sh, wo*sw] = gy[ho, wo] @ w^T, rest zero.
-      // The zeroed gap positions contribute g = 0 to the BN-backward sums,
-      // so partials over written positions alone are the full sums. With
-      // acc the gaps receive no main-branch gradient: `into` already holds
-      // their final values.
+      // With acc the gaps receive no main-branch gradient: `into` already
+      // holds their final values.
       at::Tensor gx = acc ? *into : canvas();
       if (!acc) gx.zero_();
       conv2d_fwd_into(gy, wt, gx, gy.size(2), gy.size(3), 1, 1, 0, 0, 1, 1,
-                      groups, sh, sw, 0, 0, part_out, bemit, acc);
+                      groups, sh, sw, 0, 0, nullptr, acc);
       return gx;
     }
     case DgradKind::Parity3x3: {
@@ -1366,7 +1280,6 @@ static at::Tensor conv2d_dgrad_run(DgradRoute rt, at::Tensor gy, at::Tensor w,
       // classes tile gx disjointly, so with acc each sub-conv
       // scatter-accumulates its own positions exactly once.
       at::Tensor gx = acc ? *into : canvas();
-      std::vector<at::Tensor> parts;
       for (int h0 = 0; h0 < 2; ++h0) {
         const int64_t hu = (H - h0 + 1) >> 1;
         auto wr = (h0 == 0) ? wt.slice(2, 1, 2) : wt.slice(2, 0, 3, 2);
@@ -1374,14 +1287,10 @@ static at::Tensor conv2d_dgrad_run(DgradRoute rt, at::Tensor gy, at::Tensor w,
           const int64_t wu = (W - w0 + 1) >> 1;
           auto wsub = ((w0 == 0) ? wr.slice(3, 1, 2) : wr.slice(3, 0, 3, 2))
                           .contiguous(at::MemoryFormat::ChannelsLast);
-          at::Tensor sub_part;
           conv2d_fwd_into(gy, wsub, gx, hu, wu, 1, 1, 0, 0, 1, 1, groups, 2,
-                          2, h0, w0, bemit ? &sub_part : nullptr, bemit, acc);
-          if (bemit && sub_part.defined()) parts.push_back(sub_part);
+                          2, h0, w0, nullptr, acc);
         }
       }
-      if (bemit && part_out && parts.size() == 4)
-        *part_out = at::cat(parts, 0);
       return gx;
     }
     case DgradKind::Same:
@@ -1389,9 +1298,8 @@ static at::Tensor conv2d_dgrad_run(DgradRoute rt, at::Tensor gy, at::Tensor w,
       // reaches the small and halo kernels. acc: the v1 predicated kernel.
       if (acc)
         return conv2d_fwd_into(gy, wt, *into, H, W, 1, 1, pph, ppw, dh, dw,
-                               groups, 1, 1, 0, 0, nullptr, nullptr, true);
-      return conv2d_fwd_impl(gy, wt, 1, 1, pph, ppw, dh, dw, groups, part_out,
-                             bemit);
+                               groups, 1, 1, 0, 0, nullptr, true);
+      return conv2d_fwd_impl(gy, wt, 1, 1, pph, ppw, dh, dw, groups, nullptr);
     default: {
       auto gyd = (sh == 1 && sw == 1) ? gy : dilate_nhwc(gy, sh, sw);
       TORCH_CHECK(pph >= 0 && ppw >= 0, "dgrad pad underflow");
@@ -1401,8 +1309,7 @@ static at::Tensor conv2d_dgrad_run(DgradRoute rt, at::Tensor gy, at::Tensor w,
       // past the last forward window, where forward's floor division
       // dropped input).
       auto gx = canvas();
-      conv2d_fwd_into(gyd, wt, gx, H, W, 1, 1, pph, ppw, dh, dw, groups, 1, 1,
-                      0, 0, part_out, bemit);
+      conv2d_fwd_into(gyd, wt, gx, H, W, 1, 1, pph, ppw, dh, dw, groups);
       return gx;
     }
   }
@@ -1415,7 +1322,7 @@ at::Tensor conv2d_dgrad(at::Tensor gy, at::Tensor w, int64_t H, int64_t W,
                         c10::optional<at::Tensor> pre, int64_t pre_kind) {
   return conv2d_dgrad_run(
       dgrad_route_of(gy, w, H, W, sh, sw, ph, pw, dh, dw, groups, nullptr),
-      gy, w, H, W, sh, sw, ph, pw, dh, dw, groups, nullptr, nullptr,
+      gy, w, H, W, sh, sw, ph, pw, dh, dw, groups,
       pre.has_value() ? &*pre : nullptr, pre_kind);
 }
 
@@ -1450,32 +1357,6 @@ std::tuple<std::string, int64_t, bool> conv2d_dgrad_route(
   return {dgrad_kind_name(rt.kind), rt.wkind, rt.acc};
 }
 
-// dgrad + BN-backward stat partials (docs/DESIGN_bn_conv_fusion.md, the
-// dgrad-side analogue of conv2d_fwd_bn): bnx/scale/shift/act describe the
-// BatchNorm whose gy this dgrad produces. Returns {gx, part}; part is an
-// EMPTY tensor when the dispatched kernel family doesn't emit (caller falls
-// back to the standalone reduce).
-std::vector<at::Tensor> conv2d_dgrad_bn(at::Tensor gy, at::Tensor w,
-                                        int64_t H, int64_t W, int64_t sh,
-                                        int64_t sw, int64_t ph, int64_t pw,
-                                        int64_t dh, int64_t dw,
-                                        int64_t groups, at::Tensor bnx,
-                                        at::Tensor bnscale, at::Tensor bnshift,
-                                        int64_t bnact) {
-  BnBwdEmit em;
-  em.x = (const __hip_bfloat16*)bnx.data_ptr();
-  em.scale = bnscale.data_ptr<float>();
-  em.shift = bnshift.data_ptr<float>();
-  em.act = (int)bnact;
-  at::Tensor part;
-  // (pre-transform not threaded here: the EMODE-2 path is opt-in/off)
-  auto gx = conv2d_dgrad_run(
-      dgrad_route_of(gy, w, H, W, sh, sw, ph, pw, dh, dw, groups, nullptr),
-      gy, w, H, W, sh, sw, ph, pw, dh, dw, groups, &part, &em);
-  if (!part.defined()) part = at::empty({0, 0}, bnscale.options());
-  return {gx, part};
-}
-
 // Residual-fork gradient accumulation (docs/ARCHITECTURE.md "Round-2
 // status"): compute this conv's dgrad and ADD it into `into` — the other
 // fork branch's already-computed gradient — inside the dgrad epilogue
@@ -1490,7 +1371,6 @@ std::tuple<at::Tensor, int64_t> conv2d_dgrad_acc(
   const DgradRoute rt =
       dgrad_route_of(gy, w, H, W, sh, sw, ph, pw, dh, dw, groups, &into);
   auto gx = conv2d_dgrad_run(rt, gy, w, H, W, sh, sw, ph, pw, dh, dw, groups,
-                             nullptr, nullptr,
                              pre.has_value() ? &*pre : nullptr, pre_kind,
                              &into);
   return {gx, rt.acc ? 1 : 0};

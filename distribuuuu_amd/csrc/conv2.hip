@@ -35,11 +35,6 @@ struct Conv2Params {
   int tiles_m;
   const __hip_bfloat16* xend8;  // CLAMP: last valid 16-byte load address
   float* part;  // EMIT: [tiles_m*4, 2*Kt] BN sum/sumsq partials
-  // EMODE 2: BN-backward masked stats (see conv.hip ConvParams)
-  const __hip_bfloat16* bnx;
-  const float* bnscale;
-  const float* bnshift;
-  int bnact;
 };
 
 // st_16x32 swizzle on a byte offset within a tile (1024-B subtiles)
@@ -47,16 +42,16 @@ DEV_INLINE int swz(int byte) { return byte ^ (((byte >> 9) & 1) << 5); }
 
 #define WAITVM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
 
-// EMODE: 0 plain, 1 forward BN sum/sumsq partials, 2 backward masked stats.
+// EMIT: epilogue also writes the forward BN sum/sumsq partials.
 // CLAMP: span-tail reads of the last pixels clamp to the final in-bounds
 // 16-byte address (garbage x zero-padded weight) so unaligned-span shapes
 // read x DIRECTLY instead of taking a physical-order copy with slack.
 // ACC: the epilogue ACCUMULATES into y instead of overwriting it — dgrads
 // of residual-forked tensors add straight into the BN's gres buffer and
 // the fork's separate gradient-sum kernel disappears.
-template <int EMODE, bool CLAMP = false, bool ACC = false>
+template <bool EMIT, bool CLAMP = false, bool ACC = false>
 __global__ __launch_bounds__(512) void conv_igemm_v2_kernel(Conv2Params p) {
-  static_assert(!(ACC && EMODE != 0), "ACC only with plain epilogue");
+  static_assert(!(ACC && EMIT), "ACC only with plain epilogue");
   const int g = blockIdx.z;
   int tile_m = blockIdx.x, tile_n = blockIdx.y;
   {  // XCD-aware bijective remap over m-tiles (T1)
@@ -255,63 +250,14 @@ __global__ __launch_bounds__(512) void conv_igemm_v2_kernel(Conv2Params p) {
           if (k0 + j < p.K) p.y[obase + ec + j] = u.b[j];
       }
     }
-    if (EMODE == 1) {
+    if (EMIT) {
       const int base = tile_m * BM2 + wm * 64 + mi * 16;
       bn_partial_col_accum(slab, ps, pq,
                            (int)min((int64_t)16, (int64_t)p.M - base), lane);
     }
-    if (EMODE == 2) {
-      // g = act'(x*scale+shift) * gy; two slab column passes (g, g*x)
-      union {
-        __hip_bfloat16 b[16];
-        uint4 q[2];
-      } xv;
-      const int k0 = tile_n * BN2 + wn * 64 + ec;
-      const bool valid = m < p.M;
-      if (valid) {
-        const int n = m / HoWo;
-        const int rem = m - n * HoWo;
-        const int64_t obase =
-            (((int64_t)n * p.HoA + (rem / p.Wo) * p.osh + p.oh0) * p.WoA +
-             (rem % p.Wo) * p.osw + p.ow0) * p.Kt + g * p.K;
-        if (k0 + 16 <= p.K) {
-          xv.q[0] = *reinterpret_cast<const uint4*>(&p.bnx[obase + k0]);
-          xv.q[1] = *reinterpret_cast<const uint4*>(&p.bnx[obase + k0 + 8]);
-        } else {
-          xv.q[0] = uint4{0, 0, 0, 0};
-          xv.q[1] = uint4{0, 0, 0, 0};
-#pragma unroll
-          for (int j = 0; j < 16; ++j)
-            if (k0 + j < p.K) xv.b[j] = p.bnx[obase + k0 + j];
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        float gj = 0.f;
-        if (valid) {
-          const int cc = g * p.K + k0 + j;
-          gj = to_f32(from_f32<__hip_bfloat16>(slab[er * 68 + ec + j]));
-          if (p.bnact == 1 &&
-              to_f32(xv.b[j]) * p.bnscale[cc] + p.bnshift[cc] <= 0.f)
-            gj = 0.f;
-        }
-        slab[er * 68 + ec + j] = gj;
-      }
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ps += slab[r * 68 + lane];
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        slab[er * 68 + ec + j] *= valid ? to_f32(xv.b[j]) : 0.f;
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int r = 0; r < 16; ++r) pq += slab[r * 68 + lane];
-    }
     __builtin_amdgcn_wave_barrier();
   }
-  if (EMODE != 0) {
+  if (EMIT) {
     // cross-wave (wm) combine: partial rows = tiles_m (not *4)
     float* xarea = reinterpret_cast<float*>(smem) + 8 * (16 * 68);
     if (wm > 0) {
@@ -400,26 +346,24 @@ static Conv2Params fill_v2_params(const at::Tensor& xin, const at::Tensor& wp,
   p.ksteps = R * p.nspan;
   p.tiles_m = (p.M + BM2 - 1) / BM2;
   p.part = nullptr;
-  p.bnx = nullptr; p.bnscale = nullptr; p.bnshift = nullptr; p.bnact = 0;
   return p;
 }
 
-// the one v2 launch: picks the (EMODE, CLAMP, ACC) instantiation
-template <int EMODE, bool ACC = false>
+// the one v2 launch: picks the (EMIT, CLAMP, ACC) instantiation
+template <bool EMIT, bool ACC = false>
 static void launch_v2_clamp(const Conv2Params& p, dim3 grid, bool clamp) {
   if (clamp)
-    hipLaunchKernelGGL((conv_igemm_v2_kernel<EMODE, true, ACC>), grid,
+    hipLaunchKernelGGL((conv_igemm_v2_kernel<EMIT, true, ACC>), grid,
                        dim3(512), 0, cur_stream(), p);
   else
-    hipLaunchKernelGGL((conv_igemm_v2_kernel<EMODE, false, ACC>), grid,
+    hipLaunchKernelGGL((conv_igemm_v2_kernel<EMIT, false, ACC>), grid,
                        dim3(512), 0, cur_stream(), p);
 }
-static void launch_v2(const Conv2Params& p, dim3 grid, int emode, bool clamp,
+static void launch_v2(const Conv2Params& p, dim3 grid, bool emit, bool clamp,
                       bool acc) {
-  if (emode == 2) launch_v2_clamp<2>(p, grid, clamp);
-  else if (emode == 1) launch_v2_clamp<1>(p, grid, clamp);
-  else if (acc) launch_v2_clamp<0, true>(p, grid, clamp);
-  else launch_v2_clamp<0>(p, grid, clamp);
+  if (emit) launch_v2_clamp<true>(p, grid, clamp);
+  else if (acc) launch_v2_clamp<false, true>(p, grid, clamp);
+  else launch_v2_clamp<false>(p, grid, clamp);
 }
 
 // Core launcher taking the weight ALREADY in span-padded flat [Kt, R,
@@ -429,8 +373,7 @@ at::Tensor conv2d_fwd_v2_flat(at::Tensor x, at::Tensor wp, int64_t Kt_,
                               int64_t Cg_, int64_t R_, int64_t S_, int64_t sh,
                               int64_t sw, int64_t ph, int64_t pw, int64_t dh,
                               int64_t dw, int64_t groups,
-                              at::Tensor* part_out, const BnBwdEmit* bemit,
-                              at::Tensor* acc_into) {
+                              at::Tensor* part_out, at::Tensor* acc_into) {
   CHECK_GPU(x);
   TORCH_CHECK(x.scalar_type() == at::kBFloat16, "v2: bf16 only");
   check_nhwc(x, "x");
@@ -469,8 +412,7 @@ at::Tensor conv2d_fwd_v2_flat(at::Tensor x, at::Tensor wp, int64_t Kt_,
   }
   at::Tensor y;
   if (acc_into != nullptr) {
-    TORCH_CHECK(part_out == nullptr && bemit == nullptr,
-                "v2_flat: acc excludes partial emission");
+    TORCH_CHECK(part_out == nullptr, "v2_flat: acc excludes partial emission");
     TORCH_CHECK(acc_into->sizes() ==
                     at::IntArrayRef({(int64_t)N, (int64_t)Kt, (int64_t)Ho,
                                      (int64_t)Wo}),
@@ -484,26 +426,18 @@ at::Tensor conv2d_fwd_v2_flat(at::Tensor x, at::Tensor wp, int64_t Kt_,
       fill_v2_params(xin, wp, y, N, Hp, Wp, Ct, C, K, R, S, SPAN64, Ho, Wo);
   p.sh = sh; p.sw = sw; p.dh = dh; p.dw = dw;
   dim3 grid(p.tiles_m, (K + BN2 - 1) / BN2, groups);
-  const int emode = bemit != nullptr ? 2 : part_out != nullptr ? 1 : 0;
-  if (emode != 0) {
+  if (part_out != nullptr) {
     *part_out = at::empty({(int64_t)p.tiles_m, (int64_t)2 * Kt},
                           x.options().dtype(at::kFloat));
     p.part = part_out->data_ptr<float>();
   }
-  if (bemit != nullptr) {
-    p.bnx = bemit->x;
-    p.bnscale = bemit->scale;
-    p.bnshift = bemit->shift;
-    p.bnact = bemit->act;
-  }
-  launch_v2(p, grid, emode, clamp_tail, acc_into != nullptr);
+  launch_v2(p, grid, part_out != nullptr, clamp_tail, acc_into != nullptr);
   return y;
 }
 
 at::Tensor conv2d_fwd_v2p(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
                           int64_t ph, int64_t pw, int64_t dh, int64_t dw,
-                          int64_t groups, at::Tensor* part_out,
-                          const BnBwdEmit* bemit) {
+                          int64_t groups, at::Tensor* part_out) {
   check_nhwc(w, "w");
   const int Kt = w.size(0), Cg = w.size(1), R = w.size(2), S = w.size(3);
   const int SC = S * Cg;
@@ -518,12 +452,12 @@ at::Tensor conv2d_fwd_v2p(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
                        (__hip_bfloat16*)wp.data_ptr(), Kt, R, SC, SPAN64);
   }
   return conv2d_fwd_v2_flat(x, wp, Kt, Cg, R, S, sh, sw, ph, pw, dh, dw,
-                            groups, part_out, bemit);
+                            groups, part_out);
 }
 
 at::Tensor conv2d_fwd_v2(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
                          int64_t ph, int64_t pw, int64_t dh, int64_t dw) {
-  return conv2d_fwd_v2p(x, w, sh, sw, ph, pw, dh, dw, 1, nullptr, nullptr);
+  return conv2d_fwd_v2p(x, w, sh, sw, ph, pw, dh, dw, 1, nullptr);
 }
 
 // Scatter-output variant for the pad-free dgrad routes (parity-decomposed
@@ -544,6 +478,6 @@ at::Tensor conv2d_fwd_v2_into(at::Tensor x, at::Tensor w, at::Tensor y,
       fill_v2_params(x, w, y, N, H, W, Ct, Cg, K, R, S, SC, Ho, Wo);
   p.osh = osh; p.osw = osw; p.oh0 = oh0; p.ow0 = ow0;
   dim3 grid(p.tiles_m, (K + BN2 - 1) / BN2, groups);
-  launch_v2(p, grid, 0, false, acc);
+  launch_v2(p, grid, false, false, acc);
   return y;
 }

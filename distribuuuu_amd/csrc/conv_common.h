@@ -1,18 +1,8 @@
-// What conv.hip's dispatchers share with the other conv translation units:
-// the BN-backward emission descriptor and the entry points they call.
+// The entry points of the other conv translation units that conv.hip's
+// dispatchers call.
 #pragma once
 
 #include "common.h"
-
-// BN-backward stat emission (EMODE 2) descriptor: the conv being launched is
-// a DGRAD whose output is the gy of the BatchNorm that produced this conv's
-// logical input; x/scale/shift/act describe that BN.
-struct BnBwdEmit {
-  const __hip_bfloat16* x;
-  const float* scale;
-  const float* shift;
-  int act;
-};
 
 // conv_fp32.hip: fp32 kernel path
 at::Tensor conv2d_fwd_into_fp32(at::Tensor x, at::Tensor w, at::Tensor y,
@@ -26,13 +16,12 @@ at::Tensor conv2d_fwd_into_fp32(at::Tensor x, at::Tensor w, at::Tensor y,
 // it span-padded already, _v2_into scatters into the caller's canvas.
 at::Tensor conv2d_fwd_v2p(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
                           int64_t ph, int64_t pw, int64_t dh, int64_t dw,
-                          int64_t groups, at::Tensor* part_out,
-                          const BnBwdEmit* bemit = nullptr);
+                          int64_t groups, at::Tensor* part_out);
 at::Tensor conv2d_fwd_v2_flat(at::Tensor x, at::Tensor wp, int64_t Kt_,
                               int64_t Cg_, int64_t R_, int64_t S_, int64_t sh,
                               int64_t sw, int64_t ph, int64_t pw, int64_t dh,
                               int64_t dw, int64_t groups,
-                              at::Tensor* part_out, const BnBwdEmit* bemit,
+                              at::Tensor* part_out,
                               at::Tensor* acc_into = nullptr);
 at::Tensor conv2d_fwd_v2_into(at::Tensor x, at::Tensor w, at::Tensor y,
                               int64_t Ho, int64_t Wo, int64_t groups,

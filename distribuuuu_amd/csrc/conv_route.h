@@ -86,8 +86,8 @@ inline DgradRoute dgrad_route(int64_t Kt0, int Cg, int R, int S, int sh,
                               const ConvGates& g = conv_gates()) {
   const int fCg = (int)(Kt0 / groups);  // the as-forward conv's Cg
   // stride 1 and any pad <= d*(R-1): the as-forward conv with pad
-  // d*(R-1)-pad lands on the conv-input size exactly (pad 0 is the
-  // padded-canvas BN fusion's dgrad)
+  // d*(R-1)-pad lands on the conv-input size exactly (pad 0 included: an
+  // unpadded RxS conv's dgrad stays on the ring)
   const bool fits =
       sh == 1 && sw == 1 && dh * (R - 1) >= ph && dw * (S - 1) >= pw;
   // Kept difference: the v2 gate takes every `fits` shape, while the plain

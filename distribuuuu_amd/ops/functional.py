@@ -89,7 +89,7 @@ class _HIPConv2d(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, bias, stride, padding, dilation, groups, emit_part,
-                bnx, bnscale, bnshift, bnact, bnslot, fork_slot):
+                fork_slot):
         x = _cl(x)
         w = _cl(w)
         e = ext()
@@ -132,22 +132,16 @@ class _HIPConv2d(torch.autograd.Function):
                 wt_ev = torch.cuda.Event()
                 wt_ev.record(ts)
         ctx.wt_pre = (wt_pre, wt_kind, wt_ev)
-        if bnx is not None and not cpad:
-            ctx.save_for_backward(x, w, bnx, bnscale, bnshift)
-        else:
-            ctx.save_for_backward(x, w)
+        ctx.save_for_backward(x, w)
         ctx.conf = (stride, padding, dilation, groups, bias is not None, cin,
                     kout, cpad, kpad)
-        ctx.bnact = bnact
-        ctx.bnslot = bnslot if (bnx is not None and not cpad) else None
         ctx.fork_slot = fork_slot
         ctx.mark_non_differentiable(part)
         return y, part
 
     @staticmethod
     def backward(ctx, gy, _gpart):
-        saved = ctx.saved_tensors
-        x, w = saved[0], saved[1]
+        x, w = ctx.saved_tensors
         (stride, padding, dilation, groups, has_bias, cin, kout, cpad,
          kpad) = ctx.conf
         gy = _cl(gy)
@@ -184,16 +178,6 @@ class _HIPConv2d(torch.autograd.Function):
                 # autograd run a separate whole-tensor add
                 gx, acc_done = e.conv2d_dgrad_acc(
                     *geom, fbuf, pre, pkind if pre is not None else -1)
-            elif ctx.bnslot is not None and len(saved) == 5:
-                # dgrad + BN-backward stats from the same epilogue: the
-                # consuming BN reads the partials IF this gx arrives there
-                # unmodified (data_ptr identity check in its backward)
-                bnx, bnscale, bnshift = saved[2], saved[3], saved[4]
-                gx, bpart = e.conv2d_dgrad_bn(*geom, bnx, bnscale, bnshift,
-                                              ctx.bnact)
-                if bpart.numel():
-                    ctx.bnslot["parts"].append(bpart)
-                    ctx.bnslot["gx"] = gx
             elif pre is not None:
                 gx = e.conv2d_dgrad(*geom, pre, pkind)
             else:
@@ -213,8 +197,7 @@ class _HIPConv2d(torch.autograd.Function):
                              cin, kout, cpad, kpad)
         if has_bias and ctx.needs_input_grad[2]:
             gb = gy.sum(dim=(0, 2, 3))
-        return (gx, gw, gb, None, None, None, None, None, None, None, None,
-                None, None, None)
+        return gx, gw, gb, None, None, None, None, None, None
 
 
 class _HIPDepthwiseConv2d(torch.autograd.Function):
@@ -315,31 +298,12 @@ def conv2d(x, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
             wp = _pack_narrow_groups(_cl(weight), groups, f)
             return conv2d(x, wp, bias, stride, padding, dilation, groups // f)
     if use_hip(x, "conv2d_fwd") and _hip_conv_ok(x, weight, groups):
-        if (padding != (0, 0) and x.dtype == torch.bfloat16
-                and groups == 1 and stride == (1, 1)):
-            # stride > 1 is excluded: its dgrad would lose the parity
-            # decomposition (gated on ph == 1)
-            if getattr(x, "_padded", None) == padding:
-                # producer BN already wrote the padded canvas
-                padding = (0, 0)
-            elif weight.shape[2] > 1:
-                srcbn = getattr(x, "_bn_weight", None)
-                if srcbn is not None:
-                    srcbn._bn_pad_out = padding
         emit = (bias is None and torch.is_grad_enabled()
                 and getattr(weight, "_emit_bn_partials", False))
-        info = (getattr(x, "_bn_bwd_info", None)
-                if torch.is_grad_enabled() else None)
-        if info is not None:
-            bnx, bnscale, bnshift, bnact, bnslot = info
-        else:
-            bnx = bnscale = bnshift = bnslot = None
-            bnact = 0
         fslot = (getattr(x, "_fork_slot", None)
                  if torch.is_grad_enabled() else None)
         y, part = _HIPConv2d.apply(x, weight, bias, stride, padding, dilation,
-                                   groups, emit, bnx, bnscale, bnshift, bnact,
-                                   bnslot, fslot)
+                                   groups, emit, fslot)
         if part.numel():
             y._bn_partials = part
         elif bias is None:
@@ -357,33 +321,13 @@ class _HIPBatchNormAct(torch.autograd.Function):
     """Training-mode fused BN. Stats (from conv-epilogue partials when
     available — F1) are computed in the batch_norm_act wrapper; this Function
     covers normalize(+add)(+act) forward and the backward chain, with the act
-    mask recomputed from x (F3a — the y stream is never re-read).
-
-    Backward grad-stats come from the CONSUMING conv's dgrad epilogue when it
-    emitted them (conv2d_dgrad_bn): the dgrad hands (partials, gx) through a
-    per-step slot dict, and they are used only if the incoming gy IS that gx
-    (data_ptr identity — any autograd accumulation allocates a new tensor, so
-    residual forks and multi-consumer graphs fall back automatically)."""
+    mask recomputed from x (F3a — the y stream is never re-read), or read
+    from the bitmask the residual-relu apply emitted."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, mean, rstd, scale, shift, training,
-                act_id, residual, slot, fork_slot, pad):
+                act_id, residual, fork_slot):
         e = ext()
-        if pad is not None:
-            # padded-canvas output: the consuming 3x3 v2 conv reads it
-            # pad-free (no per-step pad_image pass); backward uses the
-            # pad-aware kernels on the gy canvas
-            y = e.bn_apply_act_pad(x, scale, shift, act_id, pad[0], pad[1])
-            ctx.save_for_backward(x, weight, scale, shift, mean, rstd,
-                                  x.new_empty(0), x.new_empty(0))
-            ctx.act_id = act_id
-            ctx.training = training
-            ctx.has_res = False
-            ctx.slot = None
-            ctx.fork_slot = None
-            ctx.pad = pad
-            return y
-        ctx.pad = None
         res = _cl(residual) if residual is not None else None
         mask = None
         if (res is not None and act_id == 1 and training
@@ -400,7 +344,6 @@ class _HIPBatchNormAct(torch.autograd.Function):
         ctx.act_id = act_id
         ctx.training = training
         ctx.has_res = residual is not None
-        ctx.slot = slot
         ctx.fork_slot = fork_slot
         return y
 
@@ -408,45 +351,22 @@ class _HIPBatchNormAct(torch.autograd.Function):
     def backward(ctx, gy):
         (x, weight, scale, shift, mean, rstd, res,
          mask) = ctx.saved_tensors
-        if ctx.pad is not None:
-            e = ext()
-            gamma = weight.float().contiguous()
-            gx, gw, gb = e.bn_bwd_pad(_cl(gy), x, mean, rstd, gamma, scale,
-                                      shift, ctx.act_id, ctx.training,
-                                      ctx.pad[0], ctx.pad[1])
-            return (gx, gw.to(weight.dtype), gb.to(weight.dtype), None,
-                    None, None, None, None, None, None, None, None, None)
         if mask.numel() == 0:
             mask = None
         e = ext()
         gy = _cl(gy)
         gamma = weight.float().contiguous()
-        slot = ctx.slot
-        part = None
-        if (slot is not None and slot.get("gx") is not None
-                and len(slot["parts"]) == 1
-                and gy.data_ptr() == slot["gx"].data_ptr()):
-            part = slot["parts"][0]
-        if part is not None:
-            c = x.shape[1]
-            sums = e.bn_reduce_partials(part)
-            gx, gw, gb, gres = e.bn_bwd_apply(
-                gy, x, res if ctx.has_res else None, mean, rstd, gamma,
-                scale, shift, sums, float(x.numel() // c), ctx.act_id,
-                ctx.training, ctx.has_res)
-        else:
-            gx, gw, gb, gres = e.bn_bwd(
-                gy, x, res if ctx.has_res else None, mean, rstd, gamma,
-                scale, shift, ctx.act_id, ctx.training, ctx.has_res,
-                mask=mask)
+        gx, gw, gb, gres = e.bn_bwd(
+            gy, x, res if ctx.has_res else None, mean, rstd, gamma,
+            scale, shift, ctx.act_id, ctx.training, ctx.has_res,
+            mask=mask)
         if (ctx.has_res and ctx.fork_slot is not None
                 and "g" not in ctx.fork_slot):
             # the shortcut branch of a residual fork: deposit gres so the
             # main branch's final dgrad can accumulate into it (see _Fork)
             ctx.fork_slot["g"] = gres
         return (gx, gw.to(weight.dtype), gb.to(weight.dtype), None, None,
-                None, None, None, None, gres if ctx.has_res else None, None,
-                None, None)
+                None, None, None, None, gres if ctx.has_res else None, None)
 
 
 def _bn_stats_half(x, weight, bias, running_mean, running_var, training,
@@ -485,49 +405,12 @@ def batch_norm_act(x, weight, bias, running_mean, running_var, training=False,
         x, mean, rstd, scale, shift = _bn_stats_half(
             x, weight, bias, running_mean, running_var, training, momentum,
             eps)
-        # dgrad-side backward-stat emission is measured NET-NEGATIVE on
-        # ResNet-50 (the EMODE-2 epilogue's extra x stream + barrier
-        # serialization costs ~1.6 ms/step while removing only ~0.8 ms of
-        # bn_bwd_reduce — the residual BNs, the big tensors, can't fuse).
-        # Kept opt-in for shapes where it may win; tests force it on.
-        slot = None
-        if (training and residual is None and act_id in (0, 1)
-                and torch.is_grad_enabled()
-                and os.environ.get("DISTRIBUUUU_BN_BWD_FUSE", "0") == "1"):
-            slot = {"gx": None, "parts": []}
         res_fslot = (getattr(residual, "_fork_slot", None)
                      if residual is not None and torch.is_grad_enabled()
                      else None)
-        pad = None
-        if (residual is None and slot is None
-                and x.dtype == torch.bfloat16
-                and os.environ.get("DISTRIBUUUU_BN_PAD", "0") == "1"):
-            # measured net-negative on ResNet-50 (the pad-aware backward
-            # kernels lack the 4-row unroll and give back more than the
-            # removed pad_image pass saves) — opt-in until they catch up
-            pad = getattr(weight, "_bn_pad_out", None)
-            if pad is not None:
-                # host kernels need nrl <= W (row-incremental walk)
-                c = x.shape[1]
-                nrl, lim = 1, max(256 // max(c // 8, 1), 1)
-                while nrl * 2 <= lim:
-                    nrl *= 2
-                if c % 8 != 0 or nrl > x.shape[3]:
-                    pad = None
-        y = _HIPBatchNormAct.apply(x, weight, bias, mean, rstd, scale, shift,
-                                   training, act_id, residual, slot,
-                                   res_fslot, pad)
-        if pad is not None:
-            y._padded = pad
-        elif residual is None:
-            # discovery: a consuming padded 3x3 conv flags this weight and
-            # from the next step on the apply writes the padded canvas
-            y._bn_weight = weight
-        if slot is not None:
-            # consuming convs pick this up and emit BN-backward stats from
-            # their dgrad epilogue (see _HIPConv2d / conv2d_dgrad_bn)
-            y._bn_bwd_info = (x, scale, shift, act_id, slot)
-        return y
+        return _HIPBatchNormAct.apply(x, weight, bias, mean, rstd, scale,
+                                      shift, training, act_id, residual,
+                                      res_fslot)
     y = F.batch_norm(x, running_mean, running_var, weight, bias, training,
                      momentum, eps)
     if residual is not None:
