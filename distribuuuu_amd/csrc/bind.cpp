@@ -133,6 +133,13 @@ at::Tensor dwconv_dgrad(at::Tensor gy, at::Tensor w, int64_t H, int64_t W,
                         int64_t sh, int64_t sw, int64_t ph, int64_t pw);
 at::Tensor dwconv_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
                         int64_t sh, int64_t sw, int64_t ph, int64_t pw);
+// se_gate.hip
+std::vector<at::Tensor> se_gate_fwd(at::Tensor p, at::Tensor w1, at::Tensor b1,
+                                    at::Tensor w2, at::Tensor b2,
+                                    int64_t act);
+std::vector<at::Tensor> se_gate_bwd(at::Tensor gs, at::Tensor s, at::Tensor h,
+                                    at::Tensor z1, at::Tensor p, at::Tensor w1,
+                                    at::Tensor w2, int64_t act);
 // attention.hip
 at::Tensor mhsa_fwd(at::Tensor q, at::Tensor k, at::Tensor vt, at::Tensor rw,
                     at::Tensor rh, int64_t H, int64_t W,
@@ -178,6 +185,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dropout_fwd", &dropout_fwd);
   m.def("dropout_fwd_dev", &dropout_fwd_dev);
   m.def("se_scale_bwd", &se_scale_bwd);
+  m.def("se_gate_fwd", &se_gate_fwd);
+  m.def("se_gate_bwd", &se_gate_bwd);
   m.def("bn_sums", &bn_sums);
   m.def("bn_reduce_partials", &bn_reduce_partials);
   m.def("bn_stats", &bn_stats, py::arg("x"), py::arg("gamma"), py::arg("beta"),

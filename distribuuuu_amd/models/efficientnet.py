@@ -28,8 +28,9 @@ class SqueezeExcite(nn.Module):
         self.gate = Sigmoid()
 
     def forward(self, x):
-        s = self.avg_pool(x)
-        s = self.gate(self.conv_expand(self.act(self.conv_reduce(s))))
+        r, e = self.conv_reduce, self.conv_expand
+        s = DF.se_gate(self.avg_pool(x), r.weight, r.bias, e.weight, e.bias,
+                       "silu")
         return DF.se_scale(x, s)
 
 

@@ -46,7 +46,8 @@ class SE(nn.Module):
         self.gate = Sigmoid()
 
     def forward(self, x):
-        s = self.gate(self.fc2(self.act(self.fc1(self.avg_pool(x)))))
+        s = DF.se_gate(self.avg_pool(x), self.fc1.weight, self.fc1.bias,
+                       self.fc2.weight, self.fc2.bias, "relu")
         return DF.se_scale(x, s)
 
 

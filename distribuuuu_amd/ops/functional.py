@@ -634,6 +634,51 @@ def se_scale(x, s):
     return x * s
 
 
+class _HIPSEGate(torch.autograd.Function):
+    """The SE gate's FC-act-FC-sigmoid as two launches forward and three
+    backward (csrc/se_gate.hip), any C / Cr, no padding copies. Saves the
+    bf16 hidden h and the fp32 pre-activation z1 ([N, Cr up to 32], pad
+    columns zero) for the backward."""
+
+    @staticmethod
+    def forward(ctx, p, w1, b1, w2, b2, act):
+        s, h, z1 = ext().se_gate_fwd(p, w1, b1, w2, b2, _ACTS[act])
+        ctx.save_for_backward(p, w1, w2, s, h, z1)
+        ctx.act = _ACTS[act]
+        return s
+
+    @staticmethod
+    def backward(ctx, gs):
+        p, w1, w2, s, h, z1 = ctx.saved_tensors
+        gp, gw1, gb1, gw2, gb2, _g1, _g2 = ext().se_gate_bwd(
+            gs, s, h, z1, p, w1, w2, ctx.act)
+        return gp, gw1, gb1, gw2, gb2, None
+
+
+def se_gate(p, w1, b1, w2, b2, act):
+    """s = sigmoid(w2 * act(w1 * p + b1) + b2) for the pooled p [N, C, 1, 1]
+    (or [N, C]), 1x1 conv weights w1 [Cr, C, 1, 1], w2 [C, Cr, 1, 1] with
+    their biases and act in {"relu", "silu"} -> s [N, C, 1, 1].
+
+    bf16 GPU tensors run the fused HIP kernels; everything else (CPU, fp32,
+    DISTRIBUUUU_FORCE_TORCH, DISTRIBUUUU_SE_FUSE=0) runs the conv2d -> act ->
+    conv2d -> sigmoid composition."""
+    if act not in ("relu", "silu"):
+        raise ValueError(f"se_gate: act must be relu or silu, got {act!r}")
+    if (os.environ.get("DISTRIBUUUU_SE_FUSE", "1") != "0" and p.is_cuda
+            and b1 is not None and b2 is not None
+            and all(t.dtype == torch.bfloat16 for t in (p, w1, b1, w2, b2))
+            and w1.dim() == 4 and tuple(w1.shape[2:]) == (1, 1)
+            and w2.dim() == 4 and tuple(w2.shape[2:]) == (1, 1)
+            and use_hip(p, "se_gate_fwd")):
+        return _HIPSEGate.apply(p, w1, b1, w2, b2, act)
+    if p.dim() == 2:
+        p = p[:, :, None, None]
+    z = conv2d(p, w1, b1)
+    h = relu(z) if act == "relu" else _apply_act(z, act)
+    return _apply_act(conv2d(h, w2, b2), "sigmoid")
+
+
 class _HIPReLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

@@ -1,7 +1,7 @@
 """Per-kernel micro-benchmarks on representative ResNet-50 shapes.
 
 Usage (on a GPU box): python tools/kbench.py [--deterministic] [group ...]
-Groups: bn conv wgrad pool fused gemm sgd mix all
+Groups: bn conv wgrad pool fused gemm sgd mix se all
 Prints achieved GB/s (memory-bound ops) or TF/s (MFMA ops) per shape.
 --deterministic: the wgrad rows time each shape in both modes, atomic and
 deterministic (docs/DETERMINISM.md), side by side.
@@ -387,6 +387,50 @@ def bench_mix(passes=3):
                   f"{moved/t/1e9:7.0f} GB/s")
 
 
+def bench_se(passes=3):
+    """se_gate forward + backward: the fused kernels next to the conv2d / act /
+    conv2d / sigmoid composition (DISTRIBUUUU_SE_FUSE=0), alternated in one
+    session, on every distinct SE (C, Cr) of EfficientNet-B0 at N=256 and of
+    RegNetY-320 at N=64."""
+    import os
+
+    from distribuuuu_amd import models
+    from distribuuuu_amd.ops import functional as DF
+
+    print("== se_gate fwd+bwd, fused vs composition (us) ==")
+    for arch, n, act in (("efficientnet_b0", 256, "silu"),
+                         ("regnety_320", 64, "relu")):
+        with torch.device("meta"):
+            net = getattr(models, arch)()
+        pairs = sorted({(m.shape[1], m.shape[0])
+                        for k, m in net.state_dict().items()
+                        if k.endswith(("se.conv_reduce.weight",
+                                       "se.fc1.weight"))})
+        for c, cr in pairs:
+            bf = dict(device=DEV, dtype=torch.bfloat16)
+            args = [torch.randn(n, c, 1, 1, **bf),
+                    torch.randn(cr, c, 1, 1, **bf) / c ** 0.5,
+                    torch.zeros(cr, **bf),
+                    torch.randn(c, cr, 1, 1, **bf) / cr ** 0.5,
+                    torch.zeros(c, **bf)]
+            args = [a.requires_grad_() for a in args]
+            gs = torch.randn(n, c, 1, 1, **bf)
+
+            def step():
+                s = DF.se_gate(*args, act)
+                torch.autograd.grad(s, args, gs)
+
+            row = {"1": [], "0": []}
+            for _ in range(passes):
+                for fuse in ("1", "0"):
+                    os.environ["DISTRIBUUUU_SE_FUSE"] = fuse
+                    row[fuse].append(timeit(step, iters=100, warmup=10) * 1e6)
+            os.environ.pop("DISTRIBUUUU_SE_FUSE")
+            fmt = lambda v: " ".join(f"{t:7.1f}" for t in v)  # noqa: E731
+            print(f"{arch:16s} N={n:3d} C={c:4d} Cr={cr:3d}  fused "
+                  f"{fmt(row['1'])}   composition {fmt(row['0'])}")
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     deterministic = "--deterministic" in args
@@ -411,3 +455,5 @@ if __name__ == "__main__":
         bench_sgd()
     if "mix" in groups or "all" in groups:
         bench_mix()
+    if "se" in groups or "all" in groups:
+        bench_se()
