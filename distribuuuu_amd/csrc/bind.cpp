@@ -133,6 +133,9 @@ at::Tensor dwconv_dgrad(at::Tensor gy, at::Tensor w, int64_t H, int64_t W,
                         int64_t sh, int64_t sw, int64_t ph, int64_t pw);
 at::Tensor dwconv_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
                         int64_t sh, int64_t sw, int64_t ph, int64_t pw);
+std::tuple<std::string, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
+dwconv_route_py(at::Tensor x, int64_t R, int64_t S, int64_t sh, int64_t sw,
+                int64_t ph, int64_t pw, std::string pass);
 // se_gate.hip
 std::vector<at::Tensor> se_gate_fwd(at::Tensor p, at::Tensor w1, at::Tensor b1,
                                     at::Tensor w2, at::Tensor b2,
@@ -263,6 +266,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv_fwd", &dwconv_fwd);
   m.def("dwconv_dgrad", &dwconv_dgrad);
   m.def("dwconv_wgrad", &dwconv_wgrad);
+  m.def("dwconv_route", &dwconv_route_py);
   m.def("mhsa_fwd", &mhsa_fwd);
   m.def("mhsa_bwd", &mhsa_bwd);
   m.def("mhsa_rel_tables", &mhsa_rel_tables);

@@ -2,9 +2,34 @@
 // channel. No MFMA (K-dim per group = R*S): memory-bound elementwise-style
 // kernels over NHWC with 8-channel packs; weights [C,1,R,S] (channels_last ->
 // physical [C][R][S]) are L2-resident.
+//
+// These are the generic kernels: any R x S, stride, pad, bf16 and fp32. The
+// bf16 3x3 / 5x5 shapes that dwconv_route (dwconv_route.h) admits run the
+// LDS-tiled kernels of depthwise_tile.hip instead; the three entry points
+// below ask the route first.
 #include "common.h"
+#include "dwconv_route.h"
+
+// depthwise_tile.hip
+void dw_tile_fwd(const DwRoute& rt, const at::Tensor& x, const at::Tensor& w,
+                 at::Tensor& y, int R, int st, int ph, int pw, bool flip);
+void dw_tile_dgrad_s2(const DwRoute& rt, const at::Tensor& gy,
+                      const at::Tensor& w, at::Tensor& gx, int R, int ph,
+                      int pw);
+void dw_tile_wgrad(const DwRoute& rt, const at::Tensor& gy,
+                   const at::Tensor& x, at::Tensor& ws, int R, int st, int ph,
+                   int pw);
 
 namespace {
+
+DwRoute route_of(const at::Tensor& t, int64_t N, int64_t C, int64_t H,
+                 int64_t W, int64_t R, int64_t S, int64_t sh, int64_t sw,
+                 int64_t ph, int64_t pw, DwPass pass) {
+  const bool ok = t.scalar_type() == at::kBFloat16 && t.dim() == 4 &&
+                  t.is_contiguous(at::MemoryFormat::ChannelsLast);
+  return dwconv_route(ok, N, C, H, W, (int)R, (int)S, (int)sh, (int)sw,
+                      (int)ph, (int)pw, pass);
+}
 
 template <typename T>
 __global__ void dwconv_fwd_kernel(const T* __restrict__ x,
@@ -182,6 +207,11 @@ at::Tensor dwconv_fwd(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
   const int Ho = (H + 2 * ph - R) / sh + 1, Wo = (W + 2 * pw - S) / sw + 1;
   auto y = at::empty({N, C, Ho, Wo},
                      x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  const DwRoute rt = route_of(x, N, C, H, W, R, S, sh, sw, ph, pw, DwPass::Fwd);
+  if (rt.tiled) {
+    dw_tile_fwd(rt, x, w, y, R, sh, ph, pw, false);
+    return y;
+  }
   DISPATCH_FLOAT_AND_BF16(x.scalar_type(), "dwconv_fwd", [&] {
     constexpr int V = 16 / sizeof(scalar_t);
     TORCH_CHECK(C % V == 0, "C % ", V, " != 0");
@@ -203,6 +233,17 @@ at::Tensor dwconv_dgrad(at::Tensor gy, at::Tensor w, int64_t H, int64_t W,
   const int R = w.size(2), S = w.size(3);
   auto gx = at::empty({N, C, H, W},
                       gy.options().memory_format(at::MemoryFormat::ChannelsLast));
+  const DwRoute rt =
+      route_of(gy, N, C, H, W, R, S, sh, sw, ph, pw, DwPass::Dgrad);
+  // the route derives Ho x Wo from H x W; a gy of another extent is generic
+  if (rt.tiled && Ho == (H + 2 * ph - R) / sh + 1 &&
+      Wo == (W + 2 * pw - S) / sw + 1) {
+    if (sh == 1)  // the forward machine over gy with the taps back to front
+      dw_tile_fwd(rt, gy, w, gx, R, 1, R - 1 - ph, S - 1 - pw, true);
+    else
+      dw_tile_dgrad_s2(rt, gy, w, gx, R, ph, pw);
+    return gx;
+  }
   DISPATCH_FLOAT_AND_BF16(gy.scalar_type(), "dwconv_dgrad", [&] {
     constexpr int V = 16 / sizeof(scalar_t);
     int64_t total = (int64_t)N * H * W * (C / V);
@@ -230,6 +271,20 @@ at::Tensor dwconv_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
   auto gw_opts = x.scalar_type() == at::kBFloat16
                      ? x.options().memory_format(at::MemoryFormat::ChannelsLast)
                      : x.options();
+  const DwRoute rt =
+      route_of(x, N, C, H, W, R, S, sh, sw, ph, pw, DwPass::Wgrad);
+  if (rt.tiled && gy.scalar_type() == at::kBFloat16 &&
+      Ho == (H + 2 * ph - R) / sh + 1 && Wo == (W + 2 * pw - S) / sw + 1) {
+    // one pass, one slot per block, summed in slot order: the same bits in
+    // both determinism modes, so the flag is not read
+    auto ws = at::empty({(int64_t)rt.slots, n}, x.options().dtype(at::kFloat));
+    dw_tile_wgrad(rt, gy, x, ws, R, sh, ph, pw);
+    auto gw = at::empty({C, 1, (int64_t)R, (int64_t)S}, gw_opts);
+    ordered_reduce<__hip_bfloat16>(ws.data_ptr<float>(),
+                                   (__hip_bfloat16*)gw.data_ptr(), rt.slots, n,
+                                   1.f);
+    return gw;
+  }
   at::Tensor acc, out;
   if (!det) {  // atomic mode: a zeroed [C,1,R,S] accumulator
     acc = at::empty({C, 1, (int64_t)R, (int64_t)S},
@@ -268,4 +323,21 @@ at::Tensor dwconv_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
     return gw;
   }
   return acc.contiguous(at::MemoryFormat::ChannelsLast);
+}
+
+// (route, TH, TW, CB, NB, slots, lds_bytes) of one pass ("fwd", "dgrad",
+// "wgrad") over x [N, C, H, W]; classifies only, so meta tensors work.
+std::tuple<std::string, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
+dwconv_route_py(at::Tensor x, int64_t R, int64_t S, int64_t sh, int64_t sw,
+                int64_t ph, int64_t pw, std::string pass) {
+  TORCH_CHECK(x.dim() == 4, "x must be 4-D");
+  TORCH_CHECK(pass == "fwd" || pass == "dgrad" || pass == "wgrad",
+              "pass must be fwd, dgrad or wgrad, got ", pass);
+  const DwPass p = pass == "fwd"     ? DwPass::Fwd
+                   : pass == "dgrad" ? DwPass::Dgrad
+                                     : DwPass::Wgrad;
+  const DwRoute rt = route_of(x, x.size(0), x.size(1), x.size(2), x.size(3), R,
+                              S, sh, sw, ph, pw, p);
+  if (!rt.tiled) return {"generic", 0, 0, 0, 1, 0, 0};
+  return {"tiled", rt.TH, rt.TW, rt.CP * 8, rt.NB, rt.slots, rt.lds_bytes};
 }

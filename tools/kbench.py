@@ -1,7 +1,7 @@
 """Per-kernel micro-benchmarks on representative ResNet-50 shapes.
 
 Usage (on a GPU box): python tools/kbench.py [--deterministic] [group ...]
-Groups: bn conv wgrad pool fused gemm sgd mix se all
+Groups: bn conv wgrad pool fused gemm sgd mix se dw all
 Prints achieved GB/s (memory-bound ops) or TF/s (MFMA ops) per shape.
 --deterministic: the wgrad rows time each shape in both modes, atomic and
 deterministic (docs/DETERMINISM.md), side by side.
@@ -431,6 +431,56 @@ def bench_se(passes=3):
                   f"{fmt(row['1'])}   composition {fmt(row['0'])}")
 
 
+# EfficientNet-B0's distinct depthwise convs: (C, H, R, stride), pad R // 2
+DW_SHAPES = [(32, 112, 3, 1), (96, 112, 3, 2), (144, 56, 3, 1),
+             (144, 56, 5, 2), (240, 28, 5, 1), (240, 28, 3, 2),
+             (480, 14, 3, 1), (480, 14, 5, 1), (672, 14, 5, 1),
+             (672, 14, 5, 2), (1152, 7, 5, 1), (1152, 7, 3, 1)]
+
+
+def bench_dw(n=256, passes=3):
+    """Depthwise fwd / dgrad / wgrad: the LDS-tiled route next to the generic
+    kernels (DISTRIBUUUU_DW_TILE=0), alternated over `passes` passes in one
+    session. GB/s is against each pass's minimum traffic: every operand read
+    once and the result written once."""
+    import os
+
+    print(f"== depthwise, tiled vs generic, EfficientNet-B0 at N={n} "
+          "(us per call; GB/s of minimum traffic) ==")
+    saved = os.environ.pop("DISTRIBUUUU_DW_TILE", None)
+    try:
+        for c, h, r, s in DW_SHAPES:
+            p = r // 2
+            ho = (h + 2 * p - r) // s + 1
+            bf = dict(device=DEV, dtype=torch.bfloat16)
+            x = _cl(torch.randn(n, c, h, h, **bf))
+            wt = _cl(torch.randn(c, 1, r, r, **bf))
+            gy = _cl(torch.randn(n, c, ho, ho, **bf))
+            io = (x.numel() + gy.numel()) * 2
+            ops = (("fwd", lambda: e.dwconv_fwd(x, wt, s, s, p, p)),
+                   ("dgrad", lambda: e.dwconv_dgrad(gy, wt, h, h, s, s, p, p)),
+                   ("wgrad", lambda: e.dwconv_wgrad(gy, x, r, r, s, s, p, p)))
+            for name, fn in ops:
+                route = e.dwconv_route(x, r, r, s, s, p, p, name)
+                rows = {"1": [], "0": []}
+                for _ in range(passes):
+                    for knob in ("1", "0"):
+                        os.environ["DISTRIBUUUU_DW_TILE"] = knob
+                        rows[knob].append(timeit(fn, iters=50, warmup=5))
+                os.environ.pop("DISTRIBUUUU_DW_TILE")
+                fmt = lambda v: " ".join(  # noqa: E731
+                    f"{t*1e6:7.1f}" for t in v)
+                best = {k: min(v) for k, v in rows.items()}
+                print(f"C={c:4d} {h:3d}x{h:<3d} {r}x{r} s{s} {name:5s} "
+                      f"tiled {fmt(rows['1'])} ({io/best['1']/1e9:5.0f} GB/s)"
+                      f" | generic {fmt(rows['0'])} "
+                      f"({io/best['0']/1e9:5.0f} GB/s) | {route[:6]}")
+            del x, gy
+    finally:
+        if saved is not None:
+            os.environ["DISTRIBUUUU_DW_TILE"] = saved
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     deterministic = "--deterministic" in args
@@ -457,3 +507,5 @@ if __name__ == "__main__":
         bench_mix()
     if "se" in groups or "all" in groups:
         bench_se()
+    if "dw" in groups or "all" in groups:
+        bench_dw()
