@@ -143,6 +143,23 @@ std::vector<at::Tensor> se_gate_fwd(at::Tensor p, at::Tensor w1, at::Tensor b1,
 std::vector<at::Tensor> se_gate_bwd(at::Tensor gs, at::Tensor s, at::Tensor h,
                                     at::Tensor z1, at::Tensor p, at::Tensor w1,
                                     at::Tensor w2, int64_t act);
+// dense_bn.hip
+void dense_append(at::Tensor slab, at::Tensor y, int64_t c_off,
+                  c10::optional<at::Tensor> sums);
+at::Tensor dense_take(at::Tensor gslab, int64_t c_off, int64_t g);
+std::vector<at::Tensor> dense_bn_fwd(at::Tensor slab, int64_t cin,
+                                     c10::optional<at::Tensor> sums,
+                                     at::Tensor gamma, at::Tensor beta,
+                                     c10::optional<at::Tensor> rm_opt,
+                                     c10::optional<at::Tensor> rv_opt,
+                                     double momentum, double eps,
+                                     bool training);
+std::vector<at::Tensor> dense_bn_bwd(at::Tensor gy, at::Tensor slab,
+                                     int64_t cin,
+                                     c10::optional<at::Tensor> gslab,
+                                     at::Tensor mean, at::Tensor rstd,
+                                     at::Tensor gamma, at::Tensor scale,
+                                     at::Tensor shift, bool training);
 // attention.hip
 at::Tensor mhsa_fwd(at::Tensor q, at::Tensor k, at::Tensor vt, at::Tensor rw,
                     at::Tensor rh, int64_t H, int64_t W,
@@ -190,6 +207,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("se_scale_bwd", &se_scale_bwd);
   m.def("se_gate_fwd", &se_gate_fwd);
   m.def("se_gate_bwd", &se_gate_bwd);
+  m.def("dense_append", &dense_append, py::arg("slab"), py::arg("y"),
+        py::arg("c_off"), py::arg("sums") = py::none());
+  m.def("dense_take", &dense_take);
+  m.def("dense_bn_fwd", &dense_bn_fwd, py::arg("slab"), py::arg("cin"),
+        py::arg("sums"), py::arg("gamma"), py::arg("beta"),
+        py::arg("running_mean"), py::arg("running_var"),
+        py::arg("momentum") = 0.1, py::arg("eps") = 1e-5,
+        py::arg("training") = true);
+  m.def("dense_bn_bwd", &dense_bn_bwd, py::arg("gy"), py::arg("slab"),
+        py::arg("cin"), py::arg("gslab"), py::arg("mean"), py::arg("rstd"),
+        py::arg("gamma"), py::arg("scale"), py::arg("shift"),
+        py::arg("training") = true);
   m.def("bn_sums", &bn_sums);
   m.def("bn_reduce_partials", &bn_reduce_partials);
   m.def("bn_stats", &bn_stats, py::arg("x"), py::arg("gamma"), py::arg("beta"),

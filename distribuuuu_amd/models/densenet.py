@@ -14,7 +14,9 @@ import torch.nn as nn
 import torch.utils.checkpoint as cp
 
 from ..ops import AvgPool2d, BatchNorm2d, Conv2d, Dropout, Linear, MaxPool2d
+from ..ops import dense as DS
 from ..ops import functional as DF
+from ..ops.dispatch import use_hip
 
 
 class _DenseLayer(nn.Module):
@@ -42,6 +44,12 @@ class _DenseLayer(nn.Module):
         out = self.conv2(self.norm2(bottleneck))
         return self.drop(out)
 
+    def forward_slab(self, slab):
+        """forward() on a DenseSlab holding every previous feature: norm1
+        reads the slab's channel prefix, no concat is formed."""
+        out = self.conv2(self.norm2(self.conv1(slab.bn_relu(self.norm1))))
+        return self.drop(out)
+
 
 class _DenseBlock(nn.ModuleDict):
     def __init__(self, num_layers, num_input_features, bn_size, growth_rate,
@@ -54,7 +62,35 @@ class _DenseBlock(nn.ModuleDict):
                             bn_size, drop_rate, memory_efficient),
             )
 
+    def slab_route(self, x):
+        """Whether forward() runs concat-free on a DenseSlab (ops/dense.py):
+        GPU tensor in bf16/fp32, pack-aligned widths, every norm1 a plain
+        BatchNorm2d in the block's own mode, no checkpointing, and
+        DISTRIBUUUU_DENSE_SLAB not 0. Everything else keeps the concat."""
+        layers = list(self.values())
+        if not layers or not DS.slab_enabled():
+            return False
+        growth = layers[0].conv2.weight.shape[0]
+        c0 = layers[0].norm1.num_features
+        return (DS.slab_shape_ok(x, c0, growth) and x.shape[1] == c0
+                and all(type(m.norm1) is BatchNorm2d
+                        and m.norm1.act == "relu"
+                        and m.norm1.training == self.training
+                        and m.norm1.num_features == c0 + i * growth
+                        and m.conv2.weight.shape[0] == growth
+                        and not m.memory_efficient
+                        for i, m in enumerate(layers)))
+
     def forward(self, init_features):
+        if (self.slab_route(init_features)
+                and use_hip(init_features, "dense_append")):
+            layers = list(self.values())
+            ctot = (init_features.shape[1]
+                    + sum(m.conv2.weight.shape[0] for m in layers))
+            slab = DS.DenseSlab(init_features, ctot, self.training)
+            for layer in layers:
+                slab.append(layer.forward_slab(slab))
+            return slab.output()
         features = [init_features]
         for layer in self.values():
             features.append(layer(*features))

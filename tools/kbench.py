@@ -1,7 +1,7 @@
 """Per-kernel micro-benchmarks on representative ResNet-50 shapes.
 
 Usage (on a GPU box): python tools/kbench.py [--deterministic] [group ...]
-Groups: bn conv wgrad pool fused gemm sgd mix se dw all
+Groups: bn conv wgrad pool fused gemm sgd mix se dw dense all
 Prints achieved GB/s (memory-bound ops) or TF/s (MFMA ops) per shape.
 --deterministic: the wgrad rows time each shape in both modes, atomic and
 deterministic (docs/DETERMINISM.md), side by side.
@@ -481,6 +481,55 @@ def bench_dw(n=256, passes=3):
             os.environ["DISTRIBUUUU_DW_TILE"] = saved
 
 
+# densenet121's dense blocks: (layers, C0, H); growth 32, bn_size 4
+DENSE_BLOCKS = [(6, 64, 56), (12, 128, 28), (24, 256, 14), (16, 512, 7)]
+
+
+def bench_dense(n=128, passes=3):
+    """One dense block forward + backward in eager mode: the slab route next
+    to the concat path (DISTRIBUUUU_DENSE_SLAB=0), alternated over `passes`
+    passes in one session, on densenet121's four blocks at N=128."""
+    import os
+
+    from distribuuuu_amd.models.densenet import _DenseBlock
+
+    print(f"== dense block fwd+bwd, slab vs concat, densenet121 at N={n} "
+          "(us per block) ==")
+    saved = os.environ.pop("DISTRIBUUUU_DENSE_SLAB", None)
+    try:
+        for layers, c0, h in DENSE_BLOCKS:
+            torch.manual_seed(0)
+            block = _DenseBlock(layers, c0, 4, 32, 0.0).to(DEV).to(
+                torch.bfloat16).to(memory_format=torch.channels_last)
+            for m in block.modules():
+                if hasattr(m, "running_mean"):
+                    m.float()
+            x = _cl(torch.randn(n, c0, h, h, device=DEV,
+                                dtype=torch.bfloat16)).requires_grad_()
+            gout = _cl(torch.randn(n, c0 + 32 * layers, h, h, device=DEV,
+                                   dtype=torch.bfloat16))
+            params = [x] + list(block.parameters())
+
+            def step():
+                # the slab route accumulates into the output gradient
+                torch.autograd.grad(block(x), params, gout.clone())
+
+            rows = {"1": [], "0": []}
+            for _ in range(passes):
+                for knob in ("1", "0"):
+                    os.environ["DISTRIBUUUU_DENSE_SLAB"] = knob
+                    rows[knob].append(timeit(step, iters=20, warmup=5) * 1e6)
+            os.environ.pop("DISTRIBUUUU_DENSE_SLAB")
+            fmt = lambda v: " ".join(f"{t:8.1f}" for t in v)  # noqa: E731
+            print(f"L={layers:2d} C0={c0:3d} {h:2d}x{h:<2d}  slab "
+                  f"{fmt(rows['1'])}   concat {fmt(rows['0'])}   "
+                  f"best {min(rows['1']) / min(rows['0']):.3f}x")
+            del block, x, gout, params
+    finally:
+        if saved is not None:
+            os.environ["DISTRIBUUUU_DENSE_SLAB"] = saved
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     deterministic = "--deterministic" in args
@@ -509,3 +558,5 @@ if __name__ == "__main__":
         bench_se()
     if "dw" in groups or "all" in groups:
         bench_dw()
+    if "dense" in groups or "all" in groups:
+        bench_dense()
