@@ -136,6 +136,22 @@ at::Tensor dwconv_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
 std::tuple<std::string, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
 dwconv_route_py(at::Tensor x, int64_t R, int64_t S, int64_t sh, int64_t sw,
                 int64_t ph, int64_t pw, std::string pass);
+// gconv_tile.hip
+at::Tensor gconv_fwd(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
+                     int64_t ph, int64_t pw, int64_t groups);
+std::tuple<at::Tensor, at::Tensor> gconv_fwd_bn(at::Tensor x, at::Tensor w,
+                                                int64_t sh, int64_t sw,
+                                                int64_t ph, int64_t pw,
+                                                int64_t groups);
+at::Tensor gconv_dgrad(at::Tensor gy, at::Tensor w, int64_t H, int64_t W,
+                       int64_t sh, int64_t sw, int64_t ph, int64_t pw,
+                       int64_t groups);
+at::Tensor gconv_wgrad(at::Tensor gy, at::Tensor x, int64_t sh, int64_t sw,
+                       int64_t ph, int64_t pw, int64_t groups);
+std::tuple<std::string, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
+gconv_route_py(at::Tensor x, int64_t K, int64_t groups, int64_t R, int64_t S,
+               int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh,
+               int64_t dw, std::string pass);
 // se_gate.hip
 std::vector<at::Tensor> se_gate_fwd(at::Tensor p, at::Tensor w1, at::Tensor b1,
                                     at::Tensor w2, at::Tensor b2,
@@ -296,6 +312,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv_dgrad", &dwconv_dgrad);
   m.def("dwconv_wgrad", &dwconv_wgrad);
   m.def("dwconv_route", &dwconv_route_py);
+  m.def("gconv_fwd", &gconv_fwd);
+  m.def("gconv_fwd_bn", &gconv_fwd_bn);
+  m.def("gconv_dgrad", &gconv_dgrad);
+  m.def("gconv_wgrad", &gconv_wgrad);
+  m.def("gconv_route", &gconv_route_py);
   m.def("mhsa_fwd", &mhsa_fwd);
   m.def("mhsa_bwd", &mhsa_bwd);
   m.def("mhsa_rel_tables", &mhsa_rel_tables);

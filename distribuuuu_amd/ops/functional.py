@@ -244,6 +244,96 @@ class _HIPDepthwiseConv2d(torch.autograd.Function):
         return gx, gw, gb, None, None
 
 
+def _gconv_wgrad(e, gy, x, geom):
+    """The weight gradient has a gate of its own (gconv_route sends the one
+    measured loser back to conv2d_wgrad)."""
+    sh, sw, ph, pw, groups = geom
+    if e.gconv_route(x, x.shape[1], groups, 3, 3, sh, sw, ph, pw, 1, 1,
+                     "wgrad")[0] == "tile":
+        return e.gconv_wgrad(gy, x, *geom)
+    return e.conv2d_wgrad(gy, x, 3, 3, sh, sw, ph, pw, 1, 1, groups)
+
+
+def _cl16(t):
+    """channels_last and 16-byte aligned, as the gconv kernels' vector loads
+    need: a dense view at an odd storage offset is copied."""
+    t = _cl(t)
+    if t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.channels_last)
+    return t
+
+
+class _HIPGroupConv2d(torch.autograd.Function):
+    """Narrow-group 3x3 convs (Cg == Kg in 4/8/16/32, ResNeXt's conv2) on the
+    LDS-tiled MFMA kernels of csrc/gconv_tile.hip. The raw weight is read as
+    it is: no packing, no prep kernel. ``emit_part`` as in _HIPConv2d."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, stride, padding, groups, emit_part):
+        x = _cl16(x)
+        w = _cl16(w)
+        e = ext()
+        geom = (stride[0], stride[1], padding[0], padding[1], groups)
+        if emit_part and bias is None:
+            y, part = e.gconv_fwd_bn(x, w, *geom)
+        else:
+            y = e.gconv_fwd(x, w, *geom)
+            part = y.new_empty(0)
+        if bias is not None:
+            y = y + bias.reshape(1, -1, 1, 1)
+        ctx.save_for_backward(x, w)
+        ctx.conf = (geom, bias is not None)
+        ctx.mark_non_differentiable(part)
+        return y, part
+
+    @staticmethod
+    def backward(ctx, gy, _gpart):
+        x, w = ctx.saved_tensors
+        geom, has_bias = ctx.conf
+        gy = _cl16(gy)
+        e = ext()
+        gx = gw = gb = None
+        side = _wgrad_stream() if ctx.needs_input_grad[1] else False
+        if side is not False:
+            # co-run the wgrad with the dgrad (see _wgrad_stream)
+            main = torch.cuda.current_stream()
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                gw = _gconv_wgrad(e, gy, x, geom)
+        if ctx.needs_input_grad[0]:
+            gx = e.gconv_dgrad(gy, w, x.shape[2], x.shape[3], *geom)
+        if side is not False:
+            main.wait_stream(side)
+            if not torch.cuda.is_current_stream_capturing():
+                gw.record_stream(main)
+                gy.record_stream(side)
+                x.record_stream(side)
+        elif ctx.needs_input_grad[1]:
+            gw = _gconv_wgrad(e, gy, x, geom)
+        if has_bias and ctx.needs_input_grad[2]:
+            gb = gy.sum(dim=(0, 2, 3))
+        return gx, gw, gb, None, None, None, None
+
+
+def _gconv_tiled(x, weight, stride, padding, dilation, groups):
+    """The narrow-group route's answer for this conv (csrc/gconv_route.h).
+    Forward and data gradient share one range, so the forward's answer stands
+    for both; the weight gradient asks again (_gconv_wgrad)."""
+    if (groups < 2 or not x.is_cuda or x.dim() != 4 or weight.dim() != 4
+            or x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16
+            or weight.shape[2:] != (3, 3) or not use_hip(x, "gconv_fwd")):
+        return False
+    if not x.is_contiguous(memory_format=torch.channels_last):
+        # the kernels get _cl(x): ask for that layout without making the
+        # copy, which a "generic" answer would waste
+        x = torch.empty(x.shape, dtype=x.dtype, device="meta",
+                        memory_format=torch.channels_last)
+    return ext().gconv_route(
+        x, weight.shape[0], groups, weight.shape[2], weight.shape[3],
+        stride[0], stride[1], padding[0], padding[1], dilation[0],
+        dilation[1], "fwd")[0] == "tile"
+
+
 def _is_depthwise(x, weight, groups, dilation):
     return (groups > 1 and groups == x.shape[1] and weight.shape[0] == groups
             and weight.shape[1] == 1 and dilation == (1, 1)
@@ -289,6 +379,18 @@ def conv2d(x, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
     if (x.dtype == torch.bfloat16 and _is_depthwise(x, weight, groups, dilation)
             and use_hip(x, "dwconv_fwd")):
         return _HIPDepthwiseConv2d.apply(x, weight, bias, stride, padding)
+    if _gconv_tiled(x, weight, stride, padding, dilation, groups):
+        # the BN-partials protocol of the _HIPConv2d branch below; a
+        # _fork_slot on x is ignored, so _Fork.backward does its plain add
+        emit = (bias is None and torch.is_grad_enabled()
+                and getattr(weight, "_emit_bn_partials", False))
+        y, part = _HIPGroupConv2d.apply(x, weight, bias, stride, padding,
+                                        groups, emit)
+        if part.numel():
+            y._bn_partials = part
+        elif bias is None:
+            y._bn_src_weight = weight
+        return y
     if (x.is_cuda and groups > 1 and weight.shape[1] < 8
             and 8 % weight.shape[1] == 0
             and x.dtype in (torch.bfloat16, torch.float32)):

@@ -481,6 +481,79 @@ def bench_dw(n=256, passes=3):
             os.environ["DISTRIBUUUU_DW_TILE"] = saved
 
 
+# The in-range grouped 3x3 convs (C, w, H, stride), pad 1, of
+# resnext50_32x4d, then those only resnext101_32x8d has
+GCONV_SHAPES = [(128, 4, 56, 1), (256, 8, 56, 2), (256, 8, 28, 1),
+                (512, 16, 28, 2), (512, 16, 14, 1), (1024, 32, 14, 2),
+                (1024, 32, 7, 1),
+                (256, 8, 56, 1), (512, 16, 56, 2), (512, 16, 28, 1),
+                (1024, 32, 28, 2), (1024, 32, 14, 1)]
+
+
+def bench_gconv(n=128, passes=3):
+    """Narrow-group 3x3 conv fwd / dgrad / wgrad through functional.conv2d:
+    the LDS-tiled MFMA route next to the implicit-GEMM path
+    (DISTRIBUUUU_GCONV_TILE=0; w = 4 packs 2:1 there), alternated over
+    `passes` passes in one session. GB/s is against each pass's minimum
+    traffic: both activations once, the weight left out."""
+    import os
+
+    from distribuuuu_amd.ops import functional as DF
+
+    print(f"== grouped 3x3 conv, tile vs igemm, ResNeXt at N={n} "
+          "(us per call; GB/s of minimum traffic) ==")
+    saved = os.environ.pop("DISTRIBUUUU_GCONV_TILE", None)
+    try:
+        for c, w, h, s in GCONV_SHAPES:
+            g, ho = c // w, (h - 1) // s + 1
+            bf = dict(device=DEV, dtype=torch.bfloat16)
+            x = _cl(torch.randn(n, c, h, h, **bf)).requires_grad_()
+            wt = _cl(torch.randn(c, w, 3, 3, **bf) * 0.1).requires_grad_()
+            gy = _cl(torch.randn(n, c, ho, ho, **bf))
+            io = (x.numel() + gy.numel()) * 2
+            conv = lambda a, b: DF.conv2d(  # noqa: E731
+                a, b, None, (s, s), (1, 1), (1, 1), g)
+            # one autograd graph per route and pass: a backward runs the
+            # gradient of every input that requires one
+            yd, yw = {}, {}
+            for knob in ("1", "0"):
+                os.environ["DISTRIBUUUU_GCONV_TILE"] = knob
+                yd[knob] = conv(x, wt.detach())
+                yw[knob] = conv(x.detach(), wt)
+            os.environ.pop("DISTRIBUUUU_GCONV_TILE")
+
+            def fwd(_knob):
+                with torch.no_grad():
+                    conv(x, wt)
+
+            ops = (("fwd", fwd),
+                   ("dgrad", lambda k: torch.autograd.grad(
+                       yd[k], x, gy, retain_graph=True)),
+                   ("wgrad", lambda k: torch.autograd.grad(
+                       yw[k], wt, gy, retain_graph=True)))
+            for name, fn in ops:
+                route = e.gconv_route(x, c, g, 3, 3, s, s, 1, 1, 1, 1, name)
+                rows = {"1": [], "0": []}
+                for _ in range(passes):
+                    for knob in ("1", "0"):
+                        os.environ["DISTRIBUUUU_GCONV_TILE"] = knob
+                        rows[knob].append(timeit(lambda: fn(knob),
+                                                 iters=50, warmup=5))
+                os.environ.pop("DISTRIBUUUU_GCONV_TILE")
+                fmt = lambda v: " ".join(  # noqa: E731
+                    f"{t*1e6:7.1f}" for t in v)
+                best = {k: min(v) for k, v in rows.items()}
+                verdict = "keep" if max(rows["1"]) < min(rows["0"]) else "LOSES"
+                print(f"C={c:4d} w={w:2d} {h:3d}x{h:<3d} s{s} {name:5s} "
+                      f"tile {fmt(rows['1'])} ({io/best['1']/1e9:5.0f} GB/s)"
+                      f" | igemm {fmt(rows['0'])} "
+                      f"({io/best['0']/1e9:5.0f} GB/s) | {verdict} {route[1:]}")
+            del x, gy, yd, yw
+    finally:
+        if saved is not None:
+            os.environ["DISTRIBUUUU_GCONV_TILE"] = saved
+
+
 # densenet121's dense blocks: (layers, C0, H); growth 32, bn_size 4
 DENSE_BLOCKS = [(6, 64, 56), (12, 128, 28), (24, 256, 14), (16, 512, 7)]
 
@@ -558,5 +631,7 @@ if __name__ == "__main__":
         bench_se()
     if "dw" in groups or "all" in groups:
         bench_dw()
+    if "gconv" in groups or "all" in groups:
+        bench_gconv()
     if "dense" in groups or "all" in groups:
         bench_dense()
