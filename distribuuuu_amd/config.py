@@ -183,6 +183,9 @@ _C.TRAIN.PRINT_FREQ = 30
 _C.TRAIN.TOPK = 5
 # MI355X-native additions (defaults preserve reference behavior)
 _C.TRAIN.DTYPE = "float32"          # "float32" | "bfloat16" (bf16 compute, fp32 master)
+# fp32 conv kernels: "highest" exact fp32 MFMA | "high" 3xBF16 split MFMA
+# (ops.set_fp32_precision); no effect when DTYPE is "bfloat16"
+_C.TRAIN.FP32_PRECISION = "highest"
 _C.TRAIN.CHANNELS_LAST = False       # NHWC end-to-end
 _C.TRAIN.BUCKET_CAP_MB = 8           # DDP gradient bucket size, tuned for 7-link xGMI
 _C.TRAIN.COMPILE_GRAPH = False       # capture the train step in a hipGraph

@@ -198,6 +198,10 @@ at::Tensor aug_crop_flip_norm(at::Tensor raw, at::Tensor meta, int64_t S,
 // det_reduce.hip
 void set_deterministic(bool on);
 bool is_deterministic();
+void set_fp32_high(bool on);
+bool is_fp32_high();
+// conv_route.h via conv_fp32.hip
+std::string fp32_conv_route(int64_t Cg, int64_t Kg, std::string pass);
 // sgd.hip
 void sgd_step(at::Tensor table, double lr, double momentum,
               double dampening, double weight_decay, bool nesterov);
@@ -323,4 +327,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("aug_crop_flip_norm", &aug_crop_flip_norm);
   m.def("set_deterministic", &set_deterministic);
   m.def("is_deterministic", &is_deterministic);
+  m.def("set_fp32_precision", [](const std::string& mode) {
+    TORCH_CHECK_VALUE(mode == "highest" || mode == "high",
+                      "fp32 precision must be 'highest' or 'high', got '",
+                      mode, "'");
+    set_fp32_high(mode == "high");
+  });
+  m.def("get_fp32_precision",
+        [] { return std::string(is_fp32_high() ? "high" : "highest"); });
+  m.def("fp32_conv_route", &fp32_conv_route, py::arg("Cg"), py::arg("Kg"),
+        py::arg("pass"));
 }

@@ -154,6 +154,13 @@ inline hipStream_t cur_stream() {
 void set_deterministic(bool on);
 bool is_deterministic();
 
+// fp32 precision of the conv kernels (conv_fp32_split.hip): false = "highest",
+// exact fp32 MFMA (the default); true = "high", three bf16 MFMAs per product.
+// Process-global like the switch above, initial value from
+// DISTRIBUUUU_FP32_PRECISION=high, sampled per launch.
+void set_fp32_high(bool on);
+bool is_fp32_high();
+
 // out[i] = cast(scale * sum_{p=0..P-1, ascending} part[p*n + i]) on the
 // current stream; Tout = float or __hip_bfloat16. part is a fully written
 // [P][n] fp32 workspace (no memset needed).

@@ -12,6 +12,18 @@ at::Tensor conv2d_fwd_into_fp32(at::Tensor x, at::Tensor w, at::Tensor y,
                                 int64_t oh0, int64_t ow0,
                                 at::Tensor* part_out);
 
+// conv_fp32_split.hip: the 3xBF16 split kernels behind the two fp32 entry
+// points, taken when fp32_route_split (conv_route.h) says so
+at::Tensor conv2d_fwd_into_f32s(at::Tensor x, at::Tensor w, at::Tensor y,
+                                int64_t Ho, int64_t Wo, int64_t sh, int64_t sw,
+                                int64_t ph, int64_t pw, int64_t dh, int64_t dw,
+                                int64_t groups, int64_t osh, int64_t osw,
+                                int64_t oh0, int64_t ow0,
+                                at::Tensor* part_out);
+at::Tensor conv2d_wgrad_f32s(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
+                             int64_t sh, int64_t sw, int64_t ph, int64_t pw,
+                             int64_t dh, int64_t dw, int64_t groups);
+
 // conv2.hip: the v2 ring. _v2p pads the weight span itself, _v2_flat takes
 // it span-padded already, _v2_into scatters into the caller's canvas.
 at::Tensor conv2d_fwd_v2p(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,

@@ -15,6 +15,8 @@
 //                             m-major in LDS and read column-wise (pad
 //                             breaks conflicts), split-m fp32 atomics.
 #include "common.h"
+#include "conv_common.h"
+#include "conv_route.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4f;
 
@@ -363,6 +365,12 @@ at::Tensor conv2d_fwd_into_fp32(at::Tensor x, at::Tensor w, at::Tensor y,
                                 at::Tensor* part_out) {
   CHECK_GPU(x);
   TORCH_CHECK(x.scalar_type() == at::kFloat, "conv2d_fwd_fp32: fp32 only");
+  // "high" precision: the split kernel. Every caller is a forward conv in
+  // its own right (a dgrad arrives as the conv over gy), hence Fwd.
+  if (fp32_route_split(w.size(1), w.size(0) / groups, Fp32Pass::Fwd,
+                       is_fp32_high()))  // sampled per launch
+    return conv2d_fwd_into_f32s(x, w, y, Ho, Wo, sh, sw, ph, pw, dh, dw,
+                                groups, osh, osw, oh0, ow0, part_out);
   check_nhwc(x, "x");
   check_nhwc(w, "w");
   const int N = x.size(0), Ct = x.size(1), H = x.size(2), W = x.size(3);
@@ -404,6 +412,9 @@ at::Tensor conv2d_wgrad_fp32(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
                              int64_t dh, int64_t dw, int64_t groups) {
   CHECK_GPU(gy);
   TORCH_CHECK(gy.scalar_type() == at::kFloat, "wgrad_fp32: fp32 only");
+  if (fp32_route_split(x.size(1) / groups, gy.size(1) / groups,
+                       Fp32Pass::Wgrad, is_fp32_high()))  // sampled per launch
+    return conv2d_wgrad_f32s(gy, x, R, S, sh, sw, ph, pw, dh, dw, groups);
   check_nhwc(gy, "gy");
   check_nhwc(x, "x");
   const int N = x.size(0), Ct = x.size(1), H = x.size(2), W = x.size(3);
@@ -450,4 +461,17 @@ at::Tensor conv2d_wgrad_fp32(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
   return gwf.reshape({Kt, (int64_t)R, (int64_t)S, Cg})
       .permute({0, 3, 1, 2})
       .contiguous(at::MemoryFormat::ChannelsLast);
+}
+
+// The kernel family an fp32 conv pass with these per-group widths runs right
+// now, "split" or "exact": the answer the two launchers above act on (the
+// dgrad's as-forward conv has per-group input width Kg). Launches nothing.
+std::string fp32_conv_route(int64_t Cg, int64_t Kg, std::string pass) {
+  Fp32Pass ps;
+  if (pass == "fwd") ps = Fp32Pass::Fwd;
+  else if (pass == "dgrad") ps = Fp32Pass::Dgrad;
+  else if (pass == "wgrad") ps = Fp32Pass::Wgrad;
+  else TORCH_CHECK_VALUE(false, "fp32_conv_route: pass must be fwd, dgrad or "
+                         "wgrad, got '", pass, "'");
+  return fp32_route_split(Cg, Kg, ps, is_fp32_high()) ? "split" : "exact";
 }

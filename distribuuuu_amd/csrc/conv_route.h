@@ -108,3 +108,22 @@ inline DgradRoute dgrad_route(int64_t Kt0, int Cg, int R, int S, int sh,
     return {DgradKind::Same, 0, acc_ok};
   return {DgradKind::Dilate, 0, false};
 }
+
+// Which fp32 kernel family a conv pass runs (docs/ARCHITECTURE.md "fp32
+// split-bf16 conv"): true = the 3xBF16 split kernels of conv_fp32_split.hip,
+// false = the exact fp32 MFMA kernels of conv_fp32.hip. `high` is the
+// precision switch. Cg / Kg are the per-group widths of the FORWARD conv; the
+// data gradient runs the forward engine over gy, so its 16-byte staging rows
+// are Kg wide. Anything outside the range runs the exact kernel, which is at
+// least as accurate.
+enum class Fp32Pass { Fwd, Dgrad, Wgrad };
+
+inline bool fp32_route_split(int64_t Cg, int64_t Kg, Fp32Pass pass,
+                             bool high) {
+  if (!high) return false;
+  switch (pass) {
+    case Fp32Pass::Fwd: return Cg % 8 == 0;
+    case Fp32Pass::Dgrad: return Kg % 8 == 0;
+    default: return Cg % 8 == 0 && Kg % 8 == 0;
+  }
+}

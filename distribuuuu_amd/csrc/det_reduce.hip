@@ -23,6 +23,12 @@ std::atomic<int> g_det{[] {
   return (e && strcmp(e, "1") == 0) ? 1 : 0;
 }()};
 
+// exactly "high" turns it on (ops/dispatch.py reads the variable alike)
+std::atomic<int> g_fp32_high{[] {
+  const char* e = getenv("DISTRIBUUUU_FP32_PRECISION");
+  return (e && strcmp(e, "high") == 0) ? 1 : 0;
+}()};
+
 template <typename T>
 DEV_INLINE void store4(T* out, float a, float b, float c, float d);
 template <>
@@ -105,6 +111,9 @@ __global__ __launch_bounds__(256) void ordered_reduce_v1_kernel(
 
 void set_deterministic(bool on) { g_det.store(on ? 1 : 0); }
 bool is_deterministic() { return g_det.load() != 0; }
+
+void set_fp32_high(bool on) { g_fp32_high.store(on ? 1 : 0); }
+bool is_fp32_high() { return g_fp32_high.load() != 0; }
 
 template <typename Tout>
 void ordered_reduce(const float* part, Tout* out, int P, int64_t n,

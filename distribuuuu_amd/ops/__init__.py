@@ -11,10 +11,12 @@ extension is missing, op calls raise instead of silently falling back to ATen.
 
 from .dispatch import (  # noqa: F401
     ext,
+    get_fp32_precision,
     hip_op_available,
     is_deterministic,
     require_ext,
     set_deterministic,
+    set_fp32_precision,
 )
 from .modules import (  # noqa: F401
     AdaptiveAvgPool2d,

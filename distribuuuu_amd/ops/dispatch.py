@@ -84,6 +84,46 @@ def is_deterministic():
     return _DETERMINISTIC
 
 
+# ---------------------------------------------------------------------------
+# fp32 precision (docs/ARCHITECTURE.md "fp32 split-bf16 conv")
+# ---------------------------------------------------------------------------
+# Python-side copy of the extension's flag, as for deterministic mode above.
+# Same rule as the extension (det_reduce.hip): exactly "high" turns it on.
+_FP32_MODES = ("highest", "high")
+_FP32_PRECISION = ("high" if os.environ.get("DISTRIBUUUU_FP32_PRECISION")
+                   == "high" else "highest")
+
+
+def set_fp32_precision(mode):
+    """Choose how the fp32 conv kernels (forward, data and weight gradient,
+    and the fc GEMM that rides them) multiply.
+
+    ``"highest"`` (the default): exact fp32 MFMA. ``"high"``: every fp32
+    operand is split into two bf16 parts and each product is three bf16 MFMAs
+    with fp32 accumulation (the 3xBF16 scheme), about 2^-15 relative per
+    product; shapes the split kernels do not cover keep the exact kernel.
+    bf16 tensors are not affected.
+
+    The flag is sampled when a kernel is launched: a captured hipGraph keeps
+    the mode it was captured in.
+    """
+    global _FP32_PRECISION
+    if mode not in _FP32_MODES:
+        raise ValueError(
+            f"fp32 precision must be one of {_FP32_MODES}, got {mode!r}")
+    _FP32_PRECISION = mode
+    e = ext()
+    if e is not None:
+        e.set_fp32_precision(mode)
+
+
+def get_fp32_precision():
+    e = ext()
+    if e is not None:
+        return e.get_fp32_precision()
+    return _FP32_PRECISION
+
+
 def hip_op_available(name):
     if os.environ.get("DISTRIBUUUU_FORCE_TORCH", "0") == "1":
         return False

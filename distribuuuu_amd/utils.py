@@ -92,11 +92,13 @@ def setup_seed(rank=0):
 
     CUDNN.DETERMINISTIC is the one switch of the HIP kernels' deterministic
     mode (docs/DETERMINISM.md); RNG_SEED alone seeds and keeps the fast
-    atomic kernels. A bit-reproducible run sets both.
+    atomic kernels. A bit-reproducible run sets both. TRAIN.FP32_PRECISION
+    picks the fp32 conv kernels ("highest" exact, "high" 3xBF16 split).
     """
     from . import ops
 
     ops.set_deterministic(bool(cfg.CUDNN.DETERMINISTIC))
+    ops.set_fp32_precision(cfg.TRAIN.FP32_PRECISION)
     if rank == 0:
         os.makedirs(cfg.OUT_DIR, exist_ok=True)
         dump_cfg()

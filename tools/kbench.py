@@ -1,7 +1,7 @@
 """Per-kernel micro-benchmarks on representative ResNet-50 shapes.
 
 Usage (on a GPU box): python tools/kbench.py [--deterministic] [group ...]
-Groups: bn conv wgrad pool fused gemm sgd mix se dw dense all
+Groups: bn conv wgrad pool fused gemm sgd mix se dw gconv dense fp32 all
 Prints achieved GB/s (memory-bound ops) or TF/s (MFMA ops) per shape.
 --deterministic: the wgrad rows time each shape in both modes, atomic and
 deterministic (docs/DETERMINISM.md), side by side.
@@ -603,6 +603,58 @@ def bench_dense(n=128, passes=3):
             os.environ["DISTRIBUUUU_DENSE_SLAB"] = saved
 
 
+def bench_fp32(n=128, passes=3):
+    """fp32 conv fwd / dgrad / wgrad on ResNet-50's distinct shapes at batch
+    n: the 3xBF16 split kernels (ops.set_fp32_precision("high")) next to the
+    exact fp32 MFMA kernels ("highest"), alternated over `passes` passes in
+    one session. A (shape, pass) keeps the split route only if its slowest
+    "high" pass beats the fastest "highest" pass."""
+    from distribuuuu_amd import ops
+
+    print(f"== fp32 conv, split (high) vs exact (highest), ResNet-50 at N={n}"
+          " (us per call; TF/s of the best pass) ==")
+    was = ops.get_fp32_precision()
+    tot = {"high": 0.0, "highest": 0.0}
+    try:
+        for (nn, c, h, w_, k, r, s, p), calls in _resnet50_wgrad_shapes(n):
+            ho = (h + 2 * p - r) // s + 1
+            f32 = dict(device=DEV, dtype=torch.float32)
+            x = _cl(torch.randn(nn, c, h, w_, **f32))
+            wt = _cl(torch.randn(k, c, r, r, **f32) * 0.1)
+            gy = _cl(torch.randn(nn, k, ho, ho, **f32))
+            geom = (s, s, p, p, 1, 1, 1)
+            flops = 2.0 * nn * ho * ho * k * c * r * r
+            fns = (("fwd", lambda: e.conv2d_fwd(x, wt, *geom)),
+                   ("dgrad", lambda: e.conv2d_dgrad(gy, wt, h, w_, *geom)),
+                   ("wgrad", lambda: e.conv2d_wgrad(gy, x, r, r, *geom)))
+            for name, fn in fns:
+                rows = {"high": [], "highest": []}
+                for _ in range(passes):
+                    for mode in rows:
+                        ops.set_fp32_precision(mode)
+                        rows[mode].append(timeit(fn, iters=10, warmup=3))
+                ops.set_fp32_precision("high")
+                route = e.fp32_conv_route(c, k, name)
+                fmt = lambda v: " ".join(  # noqa: E731
+                    f"{t*1e6:8.1f}" for t in v)
+                best = {m: min(v) for m, v in rows.items()}
+                for m in tot:
+                    tot[m] += best[m] * calls
+                verdict = ("keep" if max(rows["high"]) < min(rows["highest"])
+                           else "LOSES")
+                print(f"C={c:4d} K={k:4d} {h:3d}x{h:<3d} {r}x{r} s{s} x{calls} "
+                      f"{name:5s} high {fmt(rows['high'])} "
+                      f"({flops/best['high']/1e12:5.1f} TF) | highest "
+                      f"{fmt(rows['highest'])} "
+                      f"({flops/best['highest']/1e12:5.1f} TF) | "
+                      f"{best['highest']/best['high']:.2f}x {verdict} {route}")
+            del x, wt, gy
+        print(f"sum of best x calls per step: high {tot['high']*1e3:.1f} ms, "
+              f"highest {tot['highest']*1e3:.1f} ms")
+    finally:
+        ops.set_fp32_precision(was)
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     deterministic = "--deterministic" in args
@@ -635,3 +687,5 @@ if __name__ == "__main__":
         bench_gconv()
     if "dense" in groups or "all" in groups:
         bench_dense()
+    if "fp32" in groups or "all" in groups:
+        bench_fp32()
