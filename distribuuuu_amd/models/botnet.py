@@ -18,8 +18,9 @@ import torch.nn as nn
 
 from ..ops import AdaptiveAvgPool2d, AvgPool2d, BatchNorm2d, Conv2d, Linear
 from ..ops import functional as DF
-from ..ops.attention import (check_rel_tables, hip_mhsa_supported,
-                             mhsa_relpos, mhsa_relpos_nhwc)
+from ..ops.attention import (check_rel_tables, hip_mhsa_stream_supported,
+                             hip_mhsa_supported, mhsa_relpos,
+                             mhsa_relpos_nhwc, mhsa_stream_nhwc)
 from .resnet import resnet50
 
 
@@ -59,17 +60,23 @@ class MHSA(nn.Module):
         if self.rel_pos_emb:
             check_rel_tables(self.rel_h, self.rel_w, hh, ww)
         # outside the fused kernels' range (L <= 256, H, W <= 16, head dim a
-        # multiple of 32 up to 128) mhsa_relpos below warns once and composes
+        # multiple of 32 up to 128) and the streaming kernels' (256 < L <=
+        # 1024, H, W <= 32) mhsa_relpos below warns once and composes
         if (self.rel_pos_emb and self.dim_qk == self.dim_v
-                and qk.is_cuda and qk.dtype == torch.bfloat16
-                and hip_mhsa_supported(hh, ww, self.dim_qk)):
+                and qk.is_cuda and qk.dtype == torch.bfloat16):
             from ..ops.dispatch import use_hip
-            if use_hip(qk, "mhsa_fwd"):
+            if (hip_mhsa_supported(hh, ww, self.dim_qk)
+                    and use_hip(qk, "mhsa_fwd")):
                 # NHWC in-place path: the qkv convs' channels_last outputs
                 # feed the kernels directly (no chunk/permute copies)
                 return mhsa_relpos_nhwc(qk, v, self.rel_h, self.rel_w,
                                         self.heads, self.dim_qk, self.dim_v,
                                         hh, ww, self.scale)
+            if (hip_mhsa_stream_supported(hh, ww, self.dim_qk)
+                    and use_hip(qk, "mhsa_stream_fwd")):
+                return mhsa_stream_nhwc(qk, v, self.rel_h, self.rel_w,
+                                        self.heads, self.dim_qk, hh, ww,
+                                        self.scale)
         q, k = qk.chunk(2, dim=1)
         # [N, heads, L, d]
         q = q.reshape(n, self.heads, self.dim_qk, hh * ww).transpose(2, 3)

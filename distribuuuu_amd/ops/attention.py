@@ -150,12 +150,63 @@ def hip_mhsa_supported(h, w, d):
             and d % 32 == 0 and 32 <= d <= 128)
 
 
+def hip_mhsa_stream_supported(h, w, d):
+    """Range of the streaming kernels (csrc/attention_stream.hip): maps above
+    the fused kernels' range, up to 32x32, with 64-key tiles and an online
+    softmax. L <= 256 is left to hip_mhsa_supported: a map such as 17x3 is in
+    neither range and composes."""
+    return (1 <= h <= 32 and 1 <= w <= 32 and 256 < h * w <= 1024
+            and d in (32, 64, 96, 128))
+
+
+class _HIPMHSAStream(torch.autograd.Function):
+    """Streaming forward and recompute backward for 256 < L <= 1024, dense
+    [B, L, D] layout. Saves q, k, v, the tables, O and lse [B, L] (fp32): no
+    P. The kernels build the relative-logit tables themselves and read k / v
+    transposed out of LDS, so there are no rel-table launches and no
+    [B, D, L] copies."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rel_h, rel_w, h, w):
+        n, heads, l, d = q.shape
+        bh = n * heads
+        qf = q.reshape(bh, l, d).contiguous()
+        kf = k.reshape(bh, l, d).contiguous()
+        vf = v.reshape(bh, l, d).contiguous()
+        need_grad = any(t.requires_grad for t in (q, k, v, rel_h, rel_w))
+        rel_h, rel_w = rel_h.contiguous(), rel_w.contiguous()
+        out, lse = ext().mhsa_stream_fwd(qf, kf, vf, rel_w, rel_h, l, h, w, 1,
+                                         d, d, d, 1.0, need_grad)
+        ctx.save_for_backward(qf, kf, vf, rel_h, rel_w, out, lse)
+        ctx.hw = (h, w, n, heads)
+        return out.reshape(n, heads, l, d)
+
+    @staticmethod
+    def backward(ctx, gout):
+        qf, kf, vf, rel_h, rel_w, out, lse = ctx.saved_tensors
+        h, w, n, heads = ctx.hw
+        bh, l, d = qf.shape
+        dO = gout.reshape(bh, l, d).contiguous()
+        dqk = torch.empty(2, bh, l, d, dtype=qf.dtype, device=qf.device)
+        dvb = torch.empty(bh, l, d, dtype=qf.dtype, device=qf.device)
+        dqk, dvb, grw, grh = ext().mhsa_stream_bwd(
+            dO, out, lse, qf, kf, vf, rel_w, rel_h, h, w, 1, d, bh * l * d, d,
+            d, 1.0, dqk, dvb)
+        return (dqk[0].reshape(n, heads, l, d), dqk[1].reshape(n, heads, l, d),
+                dvb.reshape(n, heads, l, d), grh.to(rel_h.dtype),
+                grw.to(rel_w.dtype), None, None)
+
+
 def mhsa_relpos(q, k, v, rel_h, rel_w, h, w):
     """q (pre-scaled), k, v: [N, heads, L, d]; returns [N, heads, L, d_v]."""
     check_rel_tables(rel_h, rel_w, h, w)
     if (use_hip(q, "mhsa_fwd") and q.dtype == torch.bfloat16
             and hip_mhsa_supported(h, w, q.shape[-1])):
         return _HIPMHSARelPos.apply(q, k, v, rel_h, rel_w, h, w)
+    if (q.dtype == torch.bfloat16 and k.shape[-1] == v.shape[-1]
+            and hip_mhsa_stream_supported(h, w, q.shape[-1])
+            and use_hip(q, "mhsa_stream_fwd")):
+        return _HIPMHSAStream.apply(q, k, v, rel_h, rel_w, h, w)
     if q.is_cuda:
         fallback_warn("mhsa_relpos",
                       f"dtype {q.dtype} head_dim {q.shape[-1]} map {h}x{w}")
@@ -230,3 +281,50 @@ def mhsa_relpos_nhwc(qk, v, rel_h, rel_w, heads, dqk, dv, h, w, scale):
     [N, heads*dv, H, W] cl."""
     return _HIPMHSARelPosNHWC.apply(qk, v, rel_h, rel_w, heads, dqk, dv, h,
                                     w, scale)
+
+
+class _HIPMHSAStreamNHWC(torch.autograd.Function):
+    """The streaming kernels on the qkv convs' channels_last outputs in place
+    (per-pixel-strided addressing as _HIPMHSARelPosNHWC). Saves qk, v, the
+    tables, O and lse: no P, no vt / kt copies."""
+
+    @staticmethod
+    def forward(ctx, qk, v, rel_h, rel_w, heads, d, h, w, scale):
+        n = qk.shape[0]
+        l = h * w
+        qkc = qk.contiguous(memory_format=torch.channels_last)
+        vc = v.contiguous(memory_format=torch.channels_last)
+        need_grad = any(t.requires_grad for t in (qk, v, rel_h, rel_w))
+        rel_h, rel_w = rel_h.contiguous(), rel_w.contiguous()
+        qpix = 2 * heads * d
+        kview = (qkc.permute(0, 2, 3, 1).reshape(n * l, qpix)
+                 [:, heads * d:])  # data_ptr offset only; kernel strides
+        out, lse = ext().mhsa_stream_fwd(qkc, kview, vc, rel_w, rel_h, l, h,
+                                         w, heads, qpix, qpix, heads * d,
+                                         scale, need_grad)
+        ctx.save_for_backward(qkc, vc, rel_h, rel_w, out, lse)
+        ctx.conf = (heads, d, h, w, scale)
+        return out  # [N, heads*d, H, W] channels_last
+
+    @staticmethod
+    def backward(ctx, gout):
+        qkc, vc, rel_h, rel_w, out, lse = ctx.saved_tensors
+        heads, d, h, w, scale = ctx.conf
+        n = qkc.shape[0]
+        qpix = 2 * heads * d
+        vpix = heads * d
+        gc = gout.contiguous(memory_format=torch.channels_last)
+        kview = qkc.permute(0, 2, 3, 1).reshape(n * h * w, qpix)[:, heads * d:]
+        dqk_out = torch.empty_like(qkc)
+        dv_out = torch.empty_like(vc)
+        dqk_out, dv_out, grw, grh = ext().mhsa_stream_bwd(
+            gc, out, lse, qkc, kview, vc, rel_w, rel_h, h, w, heads, qpix,
+            heads * d, vpix, vpix, scale, dqk_out, dv_out)
+        return (dqk_out, dv_out, grh.to(rel_h.dtype), grw.to(rel_w.dtype),
+                None, None, None, None, None)
+
+
+def mhsa_stream_nhwc(qk, v, rel_h, rel_w, heads, d, h, w, scale):
+    """qk: [N, 2*heads*d, H, W] cl; v: [N, heads*d, H, W] cl ->
+    [N, heads*d, H, W] cl, for maps in hip_mhsa_stream_supported."""
+    return _HIPMHSAStreamNHWC.apply(qk, v, rel_h, rel_w, heads, d, h, w, scale)

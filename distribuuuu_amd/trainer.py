@@ -13,6 +13,7 @@ MI355X-first deltas:
   every iteration (the reference syncs each iter — SURVEY.md §3.2 note).
 """
 
+import inspect
 import time
 
 import torch
@@ -42,10 +43,27 @@ def _prepare_batch(inputs, targets, device, dtype):
     return inputs, targets
 
 
+def build_arch(arch, im_size, num_classes):
+    """The registry call of the train and the test build. A factory that takes
+    ``fmap_size`` (BoTNet: its attention tables are sized for one map) gets
+    the stride-16 map of TRAIN.IM_SIZE, which the val loader also crops to;
+    224 gives the factory's own default of 14x14."""
+    kwargs = {"num_classes": num_classes}
+    factory = getattr(models, arch, None)
+    if (callable(factory)
+            and "fmap_size" in inspect.signature(factory).parameters):
+        if im_size % 16 != 0:
+            raise ValueError(
+                f"{arch} builds its attention for a stride-16 feature map: "
+                f"TRAIN.IM_SIZE must be a multiple of 16, got {im_size}")
+        kwargs["fmap_size"] = (im_size // 16, im_size // 16)
+    return models.build_model(arch, **kwargs)
+
+
 def build_network(device):
     """Registry build (reference trainer.py:117-128; no timm fallback — every
     baseline arch is native), optional SyncBN convert, device + layout moves."""
-    net = models.build_model(cfg.MODEL.ARCH, num_classes=cfg.MODEL.NUM_CLASSES)
+    net = build_arch(cfg.MODEL.ARCH, cfg.TRAIN.IM_SIZE, cfg.MODEL.NUM_CLASSES)
     if cfg.MODEL.SYNCBN:
         net = convert_sync_batchnorm(net)
     net = net.to(device)
@@ -250,7 +268,7 @@ def test_model():
                           else "cpu")
     setup_logger(rank, cfg.OUT_DIR)
     dtype = _compute_dtype()
-    net = models.build_model(cfg.MODEL.ARCH, num_classes=cfg.MODEL.NUM_CLASSES)
+    net = build_arch(cfg.MODEL.ARCH, cfg.TRAIN.IM_SIZE, cfg.MODEL.NUM_CLASSES)
     net = net.to(device)
     if dtype == torch.bfloat16:
         net = net.to(torch.bfloat16)

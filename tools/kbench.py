@@ -1,7 +1,8 @@
 """Per-kernel micro-benchmarks on representative ResNet-50 shapes.
 
 Usage (on a GPU box): python tools/kbench.py [--deterministic] [group ...]
-Groups: bn conv wgrad pool fused gemm sgd mix se dw gconv dense fp32 all
+Groups: bn conv wgrad pool fused gemm sgd mix se dw gconv dense fp32
+mhsa_stream all
 Prints achieved GB/s (memory-bound ops) or TF/s (MFMA ops) per shape.
 --deterministic: the wgrad rows time each shape in both modes, atomic and
 deterministic (docs/DETERMINISM.md), side by side.
@@ -655,6 +656,74 @@ def bench_fp32(n=128, passes=3):
         ops.set_fp32_precision(was)
 
 
+def bench_mhsa_stream(passes=3):
+    """Streaming MHSA (csrc/attention_stream.hip) forward + backward next to
+    the bf16 torch composition the same call took before, alternated in one
+    session: time per call and peak allocated memory above the inputs, at
+    heads = 4, D = 128 on a 24x24 map (N = 32) and a 32x32 map (N = 16).
+    Two layouts: the dense mhsa_relpos call, and the route MHSA.forward takes,
+    mhsa_stream_nhwc on the qkv convs' channels_last outputs, against the
+    chunk / transpose / compose / transpose sequence of its fallback."""
+    from distribuuuu_amd.ops.attention import (_torch_mhsa, mhsa_relpos,
+                                               mhsa_stream_nhwc)
+
+    print("== mhsa_stream fwd+bwd vs bf16 composition (ms, peak MiB) ==")
+    for n, hw in ((32, 24), (16, 32)):
+        heads, d, l = 4, 128, hw * hw
+        sc = d ** -0.5
+        bf = dict(device=DEV, dtype=torch.bfloat16)
+        q, k, v = (torch.randn(n, heads, l, d, **bf).requires_grad_()
+                   for _ in range(3))
+        rel_h, rel_w = (torch.randn(2 * hw - 1, d, **bf).mul_(sc)
+                        .requires_grad_() for _ in range(2))
+        gout = torch.randn(n, heads, l, d, **bf)
+        qk4 = _cl(torch.randn(n, 2 * heads * d, hw, hw, **bf)).requires_grad_()
+        v4 = _cl(torch.randn(n, heads * d, hw, hw, **bf)).requires_grad_()
+        gout4 = _cl(torch.randn(n, heads * d, hw, hw, **bf))
+
+        def stream():
+            out = mhsa_relpos(q * sc, k, v, rel_h, rel_w, hw, hw)
+            torch.autograd.grad(out, [q, k, v, rel_h, rel_w], gout)
+
+        def composed():
+            out = _torch_mhsa(q * sc, k, v, rel_h, rel_w, hw, hw)
+            torch.autograd.grad(out, [q, k, v, rel_h, rel_w], gout)
+
+        def stream_nhwc():
+            out = mhsa_stream_nhwc(qk4, v4, rel_h, rel_w, heads, d, hw, hw, sc)
+            torch.autograd.grad(out, [qk4, v4, rel_h, rel_w], gout4)
+
+        def composed_nhwc():  # MHSA.forward's fallback lines
+            q_, k_ = qk4.chunk(2, dim=1)
+            q_ = q_.reshape(n, heads, d, l).transpose(2, 3)
+            k_ = k_.reshape(n, heads, d, l).transpose(2, 3)
+            v_ = v4.reshape(n, heads, d, l).transpose(2, 3)
+            out = _torch_mhsa(q_ * sc, k_, v_, rel_h, rel_w, hw, hw)
+            out = out.transpose(2, 3).reshape(n, heads * d, hw, hw)
+            torch.autograd.grad(out, [qk4, v4, rel_h, rel_w], gout4)
+
+        for tag, pair in (("dense", (("stream", stream),
+                                     ("composed", composed))),
+                          ("nhwc", (("stream", stream_nhwc),
+                                    ("composed", composed_nhwc)))):
+            row = {"stream": [], "composed": []}
+            peak = {}
+            for _ in range(passes):
+                for name, fn in pair:
+                    torch.cuda.synchronize()
+                    base = torch.cuda.memory_allocated()
+                    torch.cuda.reset_peak_memory_stats()
+                    row[name].append(timeit(fn, iters=10, warmup=3) * 1e3)
+                    peak[name] = ((torch.cuda.max_memory_allocated() - base)
+                                  / 2 ** 20)
+            fmt = lambda v: " ".join(f"{t:8.2f}" for t in v)  # noqa: E731
+            print(f"N={n:3d} {hw}x{hw} heads={heads} D={d} {tag:5s} stream "
+                  f"{fmt(row['stream'])} peak {peak['stream']:8.1f}   "
+                  f"composition {fmt(row['composed'])} "
+                  f"peak {peak['composed']:8.1f}")
+        del q, k, v, gout, qk4, v4, gout4
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     deterministic = "--deterministic" in args
@@ -689,3 +758,5 @@ if __name__ == "__main__":
         bench_dense()
     if "fp32" in groups or "all" in groups:
         bench_fp32()
+    if "mhsa_stream" in groups or "all" in groups:
+        bench_mhsa_stream()
