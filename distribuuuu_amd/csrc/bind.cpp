@@ -203,6 +203,18 @@ std::vector<at::Tensor> mhsa_stream_bwd(
     at::Tensor v, at::Tensor rel_w, at::Tensor rel_h, int64_t H, int64_t W,
     int64_t heads, int64_t qpix, int64_t kqoff, int64_t vpix, int64_t opix,
     double scale, at::Tensor dqk_out, at::Tensor dv_out);
+// attention_fp32.hip
+std::vector<at::Tensor> mhsa_f32_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
+                                     at::Tensor rel_w, at::Tensor rel_h,
+                                     int64_t L, int64_t H, int64_t W,
+                                     int64_t heads, int64_t qpix, int64_t kpix,
+                                     int64_t vpix, double scale,
+                                     bool need_lse);
+std::vector<at::Tensor> mhsa_f32_bwd(
+    at::Tensor dO, at::Tensor o, at::Tensor lse, at::Tensor q, at::Tensor k,
+    at::Tensor v, at::Tensor rel_w, at::Tensor rel_h, int64_t H, int64_t W,
+    int64_t heads, int64_t qpix, int64_t kqoff, int64_t vpix, int64_t opix,
+    double scale, at::Tensor dqk_out, at::Tensor dv_out);
 // augment.hip
 at::Tensor aug_crop_flip_norm(at::Tensor raw, at::Tensor meta, int64_t S,
                               std::vector<double> mean,
@@ -338,6 +350,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mhsa_rel_tables", &mhsa_rel_tables);
   m.def("mhsa_stream_fwd", &mhsa_stream_fwd);
   m.def("mhsa_stream_bwd", &mhsa_stream_bwd);
+  m.def("mhsa_f32_fwd", &mhsa_f32_fwd);
+  m.def("mhsa_f32_bwd", &mhsa_f32_bwd);
   m.def("aug_crop_flip_norm", &aug_crop_flip_norm);
   m.def("set_deterministic", &set_deterministic);
   m.def("is_deterministic", &is_deterministic);

@@ -18,8 +18,9 @@ import torch.nn as nn
 
 from ..ops import AdaptiveAvgPool2d, AvgPool2d, BatchNorm2d, Conv2d, Linear
 from ..ops import functional as DF
-from ..ops.attention import (check_rel_tables, hip_mhsa_stream_supported,
-                             hip_mhsa_supported, mhsa_relpos,
+from ..ops.attention import (check_rel_tables, hip_mhsa_f32_supported,
+                             hip_mhsa_stream_supported, hip_mhsa_supported,
+                             mhsa_f32_enabled, mhsa_f32_nhwc, mhsa_relpos,
                              mhsa_relpos_nhwc, mhsa_stream_nhwc)
 from .resnet import resnet50
 
@@ -77,6 +78,17 @@ class MHSA(nn.Module):
                 return mhsa_stream_nhwc(qk, v, self.rel_h, self.rel_w,
                                         self.heads, self.dim_qk, hh, ww,
                                         self.scale)
+        # fp32 (the default TRAIN.DTYPE): the exact-fp32 kernels serve maps
+        # up to 32x32 in place, as the bf16 routes above (by default where
+        # they measured faster: mhsa_f32_enabled)
+        if (self.rel_pos_emb and self.dim_qk == self.dim_v and qk.is_cuda
+                and qk.dtype == torch.float32
+                and hip_mhsa_f32_supported(hh, ww, self.dim_qk)
+                and mhsa_f32_enabled(hh * ww, True)):
+            from ..ops.dispatch import use_hip
+            if use_hip(qk, "mhsa_f32_fwd"):
+                return mhsa_f32_nhwc(qk, v, self.rel_h, self.rel_w, self.heads,
+                                     self.dim_qk, hh, ww, self.scale)
         q, k = qk.chunk(2, dim=1)
         # [N, heads, L, d]
         q = q.reshape(n, self.heads, self.dim_qk, hh * ww).transpose(2, 3)

@@ -6,6 +6,8 @@ L = H*W = 196 the whole score tile fits in LDS, so no sequence partitioning is
 needed.
 """
 
+import os
+
 import torch
 import torch.nn.functional as F
 
@@ -159,6 +161,25 @@ def hip_mhsa_stream_supported(h, w, d):
             and d in (32, 64, 96, 128))
 
 
+def hip_mhsa_f32_supported(h, w, d):
+    """Range of the exact-fp32 kernels (csrc/attention_fp32.hip): one
+    streaming family for every map up to 32x32, 17x3 included."""
+    return 1 <= h <= 32 and 1 <= w <= 32 and d in (32, 64, 96, 128)
+
+
+def mhsa_f32_enabled(l, nhwc):
+    """Whether fp32 attention over l pixels takes the fp32 kernels; read per
+    call. DISTRIBUUUU_MHSA_F32=0 always composes (with the warning), =1 runs
+    the kernels on every supported map. Unset, they run where they measured
+    faster than the composition (docs/ARCHITECTURE.md, "fp32 attention"): up
+    to 24x24 in the module's in-place NHWC layout, L <= 256 in the dense one.
+    Above that they are correct and 4-7x lighter on memory, but slower."""
+    mode = os.environ.get("DISTRIBUUUU_MHSA_F32", "")
+    if mode in ("0", "1"):
+        return mode == "1"
+    return l <= (576 if nhwc else 256)
+
+
 class _HIPMHSAStream(torch.autograd.Function):
     """Streaming forward and recompute backward for 256 < L <= 1024, dense
     [B, L, D] layout. Saves q, k, v, the tables, O and lse [B, L] (fp32): no
@@ -197,6 +218,41 @@ class _HIPMHSAStream(torch.autograd.Function):
                 grw.to(rel_w.dtype), None, None)
 
 
+class _HIPMHSAF32(torch.autograd.Function):
+    """Exact-fp32 streaming forward and recompute backward, dense [B, L, D]
+    layout, any map in hip_mhsa_f32_supported. Saves q, k, v, the tables, O
+    and lse [B, L]: no P, no [B, D, L] copies."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rel_h, rel_w, h, w):
+        n, heads, l, d = q.shape
+        bh = n * heads
+        qf = q.reshape(bh, l, d).contiguous()
+        kf = k.reshape(bh, l, d).contiguous()
+        vf = v.reshape(bh, l, d).contiguous()
+        need_grad = any(t.requires_grad for t in (q, k, v, rel_h, rel_w))
+        rel_h, rel_w = rel_h.contiguous(), rel_w.contiguous()
+        out, lse = ext().mhsa_f32_fwd(qf, kf, vf, rel_w, rel_h, l, h, w, 1, d,
+                                      d, d, 1.0, need_grad)
+        ctx.save_for_backward(qf, kf, vf, rel_h, rel_w, out, lse)
+        ctx.hw = (h, w, n, heads)
+        return out.reshape(n, heads, l, d)
+
+    @staticmethod
+    def backward(ctx, gout):
+        qf, kf, vf, rel_h, rel_w, out, lse = ctx.saved_tensors
+        h, w, n, heads = ctx.hw
+        bh, l, d = qf.shape
+        dO = gout.reshape(bh, l, d).contiguous()
+        dqk = torch.empty(2, bh, l, d, dtype=qf.dtype, device=qf.device)
+        dvb = torch.empty(bh, l, d, dtype=qf.dtype, device=qf.device)
+        dqk, dvb, grw, grh = ext().mhsa_f32_bwd(
+            dO, out, lse, qf, kf, vf, rel_w, rel_h, h, w, 1, d, bh * l * d, d,
+            d, 1.0, dqk, dvb)
+        return (dqk[0].reshape(n, heads, l, d), dqk[1].reshape(n, heads, l, d),
+                dvb.reshape(n, heads, l, d), grh, grw, None, None)
+
+
 def mhsa_relpos(q, k, v, rel_h, rel_w, h, w):
     """q (pre-scaled), k, v: [N, heads, L, d]; returns [N, heads, L, d_v]."""
     check_rel_tables(rel_h, rel_w, h, w)
@@ -207,6 +263,11 @@ def mhsa_relpos(q, k, v, rel_h, rel_w, h, w):
             and hip_mhsa_stream_supported(h, w, q.shape[-1])
             and use_hip(q, "mhsa_stream_fwd")):
         return _HIPMHSAStream.apply(q, k, v, rel_h, rel_w, h, w)
+    if (q.dtype == torch.float32 and k.shape[-1] == v.shape[-1]
+            and hip_mhsa_f32_supported(h, w, q.shape[-1])
+            and mhsa_f32_enabled(h * w, False)
+            and use_hip(q, "mhsa_f32_fwd")):
+        return _HIPMHSAF32.apply(q, k, v, rel_h, rel_w, h, w)
     if q.is_cuda:
         fallback_warn("mhsa_relpos",
                       f"dtype {q.dtype} head_dim {q.shape[-1]} map {h}x{w}")
@@ -328,3 +389,51 @@ def mhsa_stream_nhwc(qk, v, rel_h, rel_w, heads, d, h, w, scale):
     """qk: [N, 2*heads*d, H, W] cl; v: [N, heads*d, H, W] cl ->
     [N, heads*d, H, W] cl, for maps in hip_mhsa_stream_supported."""
     return _HIPMHSAStreamNHWC.apply(qk, v, rel_h, rel_w, heads, d, h, w, scale)
+
+
+class _HIPMHSAF32NHWC(torch.autograd.Function):
+    """The fp32 kernels on the qkv convs' channels_last outputs in place
+    (per-pixel-strided addressing as _HIPMHSAStreamNHWC). Saves qk, v, the
+    tables, O and lse: no P, no vt / kt copies."""
+
+    @staticmethod
+    def forward(ctx, qk, v, rel_h, rel_w, heads, d, h, w, scale):
+        n = qk.shape[0]
+        l = h * w
+        qkc = qk.contiguous(memory_format=torch.channels_last)
+        vc = v.contiguous(memory_format=torch.channels_last)
+        need_grad = any(t.requires_grad for t in (qk, v, rel_h, rel_w))
+        rel_h, rel_w = rel_h.contiguous(), rel_w.contiguous()
+        qpix = 2 * heads * d
+        kview = (qkc.permute(0, 2, 3, 1).reshape(n * l, qpix)
+                 [:, heads * d:])  # data_ptr offset only; kernel strides
+        out, lse = ext().mhsa_f32_fwd(qkc, kview, vc, rel_w, rel_h, l, h, w,
+                                      heads, qpix, qpix, heads * d, scale,
+                                      need_grad)
+        if heads == 1:  # the kernel's dense [N, L, d] is the same memory
+            out = out.reshape(n, h, w, d).permute(0, 3, 1, 2)
+        ctx.save_for_backward(qkc, vc, rel_h, rel_w, out, lse)
+        ctx.conf = (heads, d, h, w, scale)
+        return out  # [N, heads*d, H, W] channels_last
+
+    @staticmethod
+    def backward(ctx, gout):
+        qkc, vc, rel_h, rel_w, out, lse = ctx.saved_tensors
+        heads, d, h, w, scale = ctx.conf
+        n = qkc.shape[0]
+        qpix = 2 * heads * d
+        vpix = heads * d
+        gc = gout.contiguous(memory_format=torch.channels_last)
+        kview = qkc.permute(0, 2, 3, 1).reshape(n * h * w, qpix)[:, heads * d:]
+        dqk_out = torch.empty_like(qkc)
+        dv_out = torch.empty_like(vc)
+        dqk_out, dv_out, grw, grh = ext().mhsa_f32_bwd(
+            gc, out, lse, qkc, kview, vc, rel_w, rel_h, h, w, heads, qpix,
+            heads * d, vpix, vpix, scale, dqk_out, dv_out)
+        return (dqk_out, dv_out, grh, grw, None, None, None, None, None)
+
+
+def mhsa_f32_nhwc(qk, v, rel_h, rel_w, heads, d, h, w, scale):
+    """fp32 qk: [N, 2*heads*d, H, W] cl; v: [N, heads*d, H, W] cl ->
+    [N, heads*d, H, W] cl, for maps in hip_mhsa_f32_supported."""
+    return _HIPMHSAF32NHWC.apply(qk, v, rel_h, rel_w, heads, d, h, w, scale)

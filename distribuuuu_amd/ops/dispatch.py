@@ -102,7 +102,8 @@ def set_fp32_precision(mode):
     operand is split into two bf16 parts and each product is three bf16 MFMAs
     with fp32 accumulation (the 3xBF16 scheme), about 2^-15 relative per
     product; shapes the split kernels do not cover keep the exact kernel.
-    bf16 tensors are not affected.
+    bf16 tensors are not affected, and neither are the fp32 attention kernels
+    (csrc/attention_fp32.hip): MHSA stays exact fp32 in both modes.
 
     The flag is sampled when a kernel is launched: a captured hipGraph keeps
     the mode it was captured in.

@@ -2,7 +2,7 @@
 
 Usage (on a GPU box): python tools/kbench.py [--deterministic] [group ...]
 Groups: bn conv wgrad pool fused gemm sgd mix se dw gconv dense fp32
-mhsa_stream all
+mhsa_stream mhsa_f32 all
 Prints achieved GB/s (memory-bound ops) or TF/s (MFMA ops) per shape.
 --deterministic: the wgrad rows time each shape in both modes, atomic and
 deterministic (docs/DETERMINISM.md), side by side.
@@ -724,6 +724,78 @@ def bench_mhsa_stream(passes=3):
         del q, k, v, gout, qk4, v4, gout4
 
 
+class _Const(torch.nn.Module):
+    """Stands in for a conv whose output is already recorded."""
+
+    def __init__(self, t):
+        super().__init__()
+        self.t = [t]
+
+    def forward(self, x):
+        return self.t[0]
+
+
+def bench_mhsa_f32(passes=3):
+    """Exact-fp32 MHSA (csrc/attention_fp32.hip) forward + backward next to
+    the fp32 torch composition the same call took before
+    (DISTRIBUUUU_MHSA_F32=0), alternated in one session: time per call and
+    peak allocated memory above the inputs, at heads = 4, D = 128 on 14x14
+    (N = 64), 24x24 (N = 32) and 32x32 (N = 16). Two layouts: the dense
+    mhsa_relpos call, and the route MHSA.forward takes (the module's own lines
+    from the qkv convs' channels_last outputs on)."""
+    import os
+    import warnings
+
+    from distribuuuu_amd.models.botnet import MHSA
+    from distribuuuu_amd.ops.attention import mhsa_relpos
+
+    print("== mhsa_f32 fwd+bwd vs fp32 composition (ms, peak MiB) ==")
+    for n, hw in ((64, 14), (32, 24), (16, 32)):
+        heads, d, l = 4, 128, hw * hw
+        sc = d ** -0.5
+        f32 = dict(device=DEV, dtype=torch.float32)
+        q, k, v = (torch.randn(n, heads, l, d, **f32).requires_grad_()
+                   for _ in range(3))
+        gout = torch.randn(n, heads, l, d, **f32)
+        # the module with its two convs replaced by their recorded outputs
+        m = MHSA(8, (hw, hw), heads=heads, dim_qk=d, dim_v=d).to(DEV)
+        qk4 = _cl(torch.randn(n, 2 * heads * d, hw, hw, **f32)).requires_grad_()
+        v4 = _cl(torch.randn(n, heads * d, hw, hw, **f32)).requires_grad_()
+        gout4 = _cl(torch.randn(n, heads * d, hw, hw, **f32))
+        m.to_qk, m.to_v = _Const(qk4), _Const(v4)
+        x0 = torch.empty(n, 8, hw, hw, **f32)
+
+        def dense():
+            out = mhsa_relpos(q * sc, k, v, m.rel_h, m.rel_w, hw, hw)
+            torch.autograd.grad(out, [q, k, v, m.rel_h, m.rel_w], gout)
+
+        def nhwc():
+            torch.autograd.grad(m(x0), [qk4, v4, m.rel_h, m.rel_w], gout4)
+
+        for tag, fn in (("dense", dense), ("nhwc", nhwc)):
+            row = {"1": [], "0": []}
+            peak = {}
+            try:
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")  # the composition warns
+                    for _ in range(passes):
+                        for on in ("1", "0"):
+                            os.environ["DISTRIBUUUU_MHSA_F32"] = on
+                            torch.cuda.synchronize()
+                            base = torch.cuda.memory_allocated()
+                            torch.cuda.reset_peak_memory_stats()
+                            row[on].append(timeit(fn, iters=10, warmup=3) * 1e3)
+                            peak[on] = ((torch.cuda.max_memory_allocated()
+                                         - base) / 2 ** 20)
+            finally:
+                os.environ.pop("DISTRIBUUUU_MHSA_F32")
+            fmt = lambda v: " ".join(f"{t:8.2f}" for t in v)  # noqa: E731
+            print(f"N={n:3d} {hw}x{hw} heads={heads} D={d} {tag:5s} kernels "
+                  f"{fmt(row['1'])} peak {peak['1']:8.1f}   "
+                  f"composition {fmt(row['0'])} peak {peak['0']:8.1f}")
+        del q, k, v, gout, qk4, v4, gout4, m
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     deterministic = "--deterministic" in args
@@ -760,3 +832,5 @@ if __name__ == "__main__":
         bench_fp32()
     if "mhsa_stream" in groups or "all" in groups:
         bench_mhsa_stream()
+    if "mhsa_f32" in groups or "all" in groups:
+        bench_mhsa_f32()
