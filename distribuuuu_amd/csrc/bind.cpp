@@ -136,6 +136,16 @@ at::Tensor dwconv_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
 std::tuple<std::string, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
 dwconv_route_py(at::Tensor x, int64_t R, int64_t S, int64_t sh, int64_t sw,
                 int64_t ph, int64_t pw, std::string pass);
+// depthwise_f32.hip
+at::Tensor dwconv_f32_fwd(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
+                          int64_t ph, int64_t pw);
+at::Tensor dwconv_f32_dgrad(at::Tensor gy, at::Tensor w, int64_t H, int64_t W,
+                            int64_t sh, int64_t sw, int64_t ph, int64_t pw);
+at::Tensor dwconv_f32_wgrad(at::Tensor gy, at::Tensor x, int64_t R, int64_t S,
+                            int64_t sh, int64_t sw, int64_t ph, int64_t pw);
+std::tuple<std::string, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
+dwconv_f32_route_py(at::Tensor x, int64_t R, int64_t S, int64_t sh, int64_t sw,
+                    int64_t ph, int64_t pw, std::string pass);
 // gconv_tile.hip
 at::Tensor gconv_fwd(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
                      int64_t ph, int64_t pw, int64_t groups);
@@ -340,6 +350,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv_dgrad", &dwconv_dgrad);
   m.def("dwconv_wgrad", &dwconv_wgrad);
   m.def("dwconv_route", &dwconv_route_py);
+  m.def("dwconv_f32_fwd", &dwconv_f32_fwd);
+  m.def("dwconv_f32_dgrad", &dwconv_f32_dgrad);
+  m.def("dwconv_f32_wgrad", &dwconv_f32_wgrad);
+  m.def("dwconv_f32_route", &dwconv_f32_route_py);
   m.def("gconv_fwd", &gconv_fwd);
   m.def("gconv_fwd_bn", &gconv_fwd_bn);
   m.def("gconv_dgrad", &gconv_dgrad);

@@ -118,3 +118,98 @@ inline DwRoute dwconv_route(bool bf16_nhwc, int64_t N, int64_t C, int64_t H,
   r.tiled = true;
   return r;
 }
+
+// ---------------------------------------------------------------------------
+// fp32 (depthwise_f32.hip; docs/ARCHITECTURE.md "Depthwise", fp32 subsection)
+// ---------------------------------------------------------------------------
+// A pack is four fp32 channels. 8 packs per chunk: 32 channels, one 128 B
+// line per pixel, so the 40 KiB budget holds twice the pixels a 16-pack chunk
+// would and a 5x5 tile keeps 8 output rows, not 2.
+constexpr int DWF_MAX_CP = 8;
+constexpr int DWF_MAX_TH = 16;  // two 1 x TW/2 strips per row: 32 per tile
+constexpr int DWF_QW = 8;       // stride-2 dgrad: quads per tile row
+
+// wgrad's end-of-run tree holds one tap row of every lane
+constexpr int dwf_red_bytes(int R) { return DW_THREADS * R * 16; }
+
+// Rows per tile as dw_pick_rows, then evened out again over the tiles left.
+template <typename F>
+inline int dwf_pick_rows(int rows, int max_th, F lds) {
+  int th = dw_ceil(rows, dw_ceil(rows, max_th));
+  while (th > 1 && lds(th) > DW_LDS_BUDGET) --th;
+  return dw_ceil(rows, dw_ceil(rows, th));
+}
+
+// As dwconv_route, for fp32 NHWC x [N, C, H, W]. CP counts packs of 4
+// channels; TW / 2 is the forward strip, TH / 2 the stride-2 dgrad's quad
+// rows. The three passes of a conv are routed together (functional.conv2d
+// asks all three), so a shape that loses is sent back here for every pass.
+inline DwRoute dwconv_f32_route(bool f32_nhwc, int64_t N, int64_t C, int64_t H,
+                                int64_t W, int R, int S, int sh, int sw,
+                                int ph, int pw, DwPass pass,
+                                bool enabled = dw_tile_enabled()) {
+  DwRoute r;
+  if (!enabled || !f32_nhwc || N < 1 || C < 4 || C % 4 != 0 || R != S ||
+      (R != 3 && R != 5) || sh != sw || (sh != 1 && sh != 2) || ph < 0 ||
+      pw < 0 || ph > R / 2 || pw > R / 2 || H + 2 * ph < R || W + 2 * pw < S ||
+      H > (1 << 20) || W > (1 << 20))
+    return r;
+  const int st = sh;
+  const int Ho = (int)((H + 2 * ph - R) / st + 1);
+  const int Wo = (int)((W + 2 * pw - S) / st + 1);
+  const int cpacks = (int)(C / 4);
+  r.nchunk = dw_ceil(cpacks, DWF_MAX_CP);
+  r.CP = dw_ceil(cpacks, r.nchunk);
+  const int nlanes = DW_THREADS / r.CP;
+  const int wbytes = R * S * r.CP * 16;
+
+  if (pass == DwPass::Dgrad && st == 2) {
+    // 2x2 parity quads of gx over u = h + ph, v = w + pw; a thread owns two
+    // neighbouring quads, a tile is DWF_QW quads wide
+    const int qrows = dw_ceil(H + ph, 2), qcols = dw_ceil(W + pw, 2);
+    auto lds = [&](int qh) {
+      return wbytes + (qh + R / 2) * (DWF_QW + R / 2) * r.CP * 16;
+    };
+    const int qh = dwf_pick_rows(qrows, DW_MAX_TH, lds);
+    r.TH = 2 * qh;
+    r.TW = 2 * DWF_QW;
+    r.tilesH = dw_ceil(qrows, qh);
+    r.tilesW = dw_ceil(qcols, DWF_QW);
+    r.lds_bytes = lds(qh);
+  } else {
+    const bool dg = pass == DwPass::Dgrad;
+    const int OH = dg ? (int)H : Ho, OW = dg ? (int)W : Wo;
+    r.TW = (st == 1 && OW > 8) ? 16 : 8;
+    const int PW = (r.TW - 1) * st + R;
+    auto lds = [&](int th, int nb = 1) {
+      const int patch = ((th - 1) * st + R) * PW * r.CP * 16;
+      if (pass == DwPass::Wgrad)
+        return std::max(patch + th * r.TW * r.CP * 16, dwf_red_bytes(R));
+      return wbytes + nb * patch;
+    };
+    // wgrad's 1x4 pixel strips fill the lanes at 8 rows already
+    r.TH = dwf_pick_rows(OH, pass == DwPass::Wgrad ? DW_MAX_TH : DWF_MAX_TH,
+                         [&](int th) { return lds(th); });
+    r.tilesH = dw_ceil(OH, r.TH);
+    r.tilesW = dw_ceil(OW, r.TW);
+    // a map that is one tile: several images per block until the strips
+    // (two per row) cover the block's lanes
+    if (pass != DwPass::Wgrad && r.tilesH == 1 && r.tilesW == 1)
+      while (r.NB < N && r.NB * r.TH * 2 < nlanes &&
+             lds(r.TH, r.NB + 1) <= DW_LDS_BUDGET)
+        ++r.NB;
+    r.lds_bytes = lds(r.TH, r.NB);
+  }
+  if (r.lds_bytes > DW_LDS_BUDGET) return r;
+
+  const int64_t items = (int64_t)dw_ceil(N, r.NB) * r.tilesH * r.tilesW;
+  if (items * r.nchunk >= ((int64_t)1 << 31)) return r;
+  if (pass == DwPass::Wgrad) {
+    const int64_t want = std::clamp<int64_t>(
+        dw_ceil(DW_FILL_BLOCKS, r.nchunk), 1, std::min<int64_t>(DW_MAX_SLOTS, items));
+    const int64_t per = (items + want - 1) / want;
+    r.slots = (int)((items + per - 1) / per);
+  }
+  r.tiled = true;
+  return r;
+}

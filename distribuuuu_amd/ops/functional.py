@@ -201,35 +201,45 @@ class _HIPConv2d(torch.autograd.Function):
 
 
 class _HIPDepthwiseConv2d(torch.autograd.Function):
+    """``pre`` names the kernel family: "dwconv" (bf16 tiled / generic) or
+    "dwconv_f32" (the exact-fp32 tiled kernels, csrc/depthwise_f32.hip)."""
+
     @staticmethod
-    def forward(ctx, x, w, bias, stride, padding):
-        x = _cl(x)
-        w = _cl(w)
-        y = ext().dwconv_fwd(x, w, stride[0], stride[1], padding[0], padding[1])
+    def forward(ctx, x, w, bias, stride, padding, pre="dwconv"):
+        x = _cl16(x)
+        w = _cl16(w)
+        y = getattr(ext(), pre + "_fwd")(x, w, stride[0], stride[1],
+                                         padding[0], padding[1])
         if bias is not None:
             y = y + bias.reshape(1, -1, 1, 1)
         ctx.save_for_backward(x, w)
-        ctx.conf = (stride, padding, bias is not None)
+        ctx.conf = (stride, padding, bias is not None, pre)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        stride, padding, has_bias = ctx.conf
-        gy = _cl(gy)
+        stride, padding, has_bias, pre = ctx.conf
+        gy = _cl16(gy)
         e = ext()
         gx = gw = gb = None
+
+        def wgrad():
+            return getattr(e, pre + "_wgrad")(
+                gy, x, w.shape[2], w.shape[3], stride[0], stride[1],
+                padding[0], padding[1])
+
         side = _wgrad_stream() if ctx.needs_input_grad[1] else False
         if side is not False:
             # co-run the depthwise wgrad with the dgrad (see _wgrad_stream)
             main = torch.cuda.current_stream()
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                gw = e.dwconv_wgrad(gy, x, w.shape[2], w.shape[3], stride[0],
-                                    stride[1], padding[0], padding[1])
+                gw = wgrad()
         if ctx.needs_input_grad[0]:
-            gx = e.dwconv_dgrad(gy, w, x.shape[2], x.shape[3], stride[0],
-                                stride[1], padding[0], padding[1])
+            gx = getattr(e, pre + "_dgrad")(
+                gy, w, x.shape[2], x.shape[3], stride[0], stride[1],
+                padding[0], padding[1])
         if side is not False:
             main.wait_stream(side)
             if not torch.cuda.is_current_stream_capturing():
@@ -237,11 +247,10 @@ class _HIPDepthwiseConv2d(torch.autograd.Function):
                 gy.record_stream(side)
                 x.record_stream(side)
         elif ctx.needs_input_grad[1]:
-            gw = e.dwconv_wgrad(gy, x, w.shape[2], w.shape[3], stride[0],
-                                stride[1], padding[0], padding[1])
+            gw = wgrad()
         if has_bias and ctx.needs_input_grad[2]:
             gb = gy.sum(dim=(0, 2, 3))
-        return gx, gw, gb, None, None
+        return gx, gw, gb, None, None, None
 
 
 def _gconv_wgrad(e, gy, x, geom):
@@ -340,6 +349,27 @@ def _is_depthwise(x, weight, groups, dilation):
             and x.shape[1] % 8 == 0)
 
 
+def _dw_f32_tiled(x, weight, stride, padding, dilation, groups):
+    """An fp32 depthwise conv that the exact-fp32 tiled kernels take
+    (dwconv_f32_route, csrc/dwconv_route.h). The tiled Function and the packed
+    conv are different autograd nodes, so the three passes are asked together
+    and move together."""
+    if (not x.is_cuda or x.dim() != 4 or weight.dim() != 4
+            or x.dtype != torch.float32 or weight.dtype != torch.float32
+            or groups < 4 or groups != x.shape[1] or groups % 4 != 0
+            or weight.shape[0] != groups or weight.shape[1] != 1
+            or dilation != (1, 1) or len(stride) != 2 or len(padding) != 2
+            or not use_hip(x, "dwconv_f32_fwd")):
+        return False
+    if not x.is_contiguous(memory_format=torch.channels_last):
+        # the kernels get _cl16(x): ask for that layout without the copy
+        x = torch.empty(x.shape, dtype=x.dtype, device="meta",
+                        memory_format=torch.channels_last)
+    r, s = weight.shape[2:]
+    return all(ext().dwconv_f32_route(x, r, s, *stride, *padding, p)[0]
+               == "tiled" for p in ("fwd", "dgrad", "wgrad"))
+
+
 def _hip_conv_ok(x, weight, groups):
     if x.dtype not in (torch.bfloat16, torch.float32):
         fallback_warn("conv2d", f"dtype {x.dtype} (bf16/fp32 MFMA kernels)")
@@ -391,6 +421,9 @@ def conv2d(x, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
         elif bias is None:
             y._bn_src_weight = weight
         return y
+    if _dw_f32_tiled(x, weight, stride, padding, dilation, groups):
+        return _HIPDepthwiseConv2d.apply(x, weight, bias, stride, padding,
+                                         "dwconv_f32")
     if (x.is_cuda and groups > 1 and weight.shape[1] < 8
             and 8 % weight.shape[1] == 0
             and x.dtype in (torch.bfloat16, torch.float32)):

@@ -482,6 +482,75 @@ def bench_dw(n=256, passes=3):
             os.environ["DISTRIBUUUU_DW_TILE"] = saved
 
 
+def bench_dw_f32(n=128, passes=3):
+    """fp32 depthwise fwd / dgrad / wgrad through functional.conv2d: the
+    exact-fp32 tiled route next to the path the same call took before
+    (DISTRIBUUUU_DW_TILE=0: eight channels packed into a block-diagonal group
+    on the fp32 implicit GEMM), alternated over `passes` passes in one
+    session. GB/s is against each pass's minimum traffic: both activations
+    once. A conv keeps the route only if the sum of its three tiled passes
+    beats the packed path in every pass."""
+    import os
+
+    from distribuuuu_amd.ops import functional as DF
+
+    print(f"== fp32 depthwise, tiled vs packed igemm, EfficientNet-B0 at "
+          f"N={n} (us per call; GB/s of minimum traffic) ==")
+    saved = os.environ.pop("DISTRIBUUUU_DW_TILE", None)
+    try:
+        for c, h, r, s in DW_SHAPES:
+            p = r // 2
+            ho = (h + 2 * p - r) // s + 1
+            f32 = dict(device=DEV, dtype=torch.float32)
+            x = _cl(torch.randn(n, c, h, h, **f32)).requires_grad_()
+            wt = _cl(torch.randn(c, 1, r, r, **f32)).requires_grad_()
+            gy = _cl(torch.randn(n, c, ho, ho, **f32))
+            io = (x.numel() + gy.numel()) * 4
+            conv = lambda a, b: DF.conv2d(  # noqa: E731
+                a, b, None, (s, s), (p, p), (1, 1), c)
+            # one autograd graph per route and pass, as in bench_gconv
+            yd, yw = {}, {}
+            for knob in ("1", "0"):
+                os.environ["DISTRIBUUUU_DW_TILE"] = knob
+                yd[knob] = conv(x, wt.detach())
+                yw[knob] = conv(x.detach(), wt)
+
+            def fwd(_knob):
+                with torch.no_grad():
+                    conv(x, wt)
+
+            ops = (("fwd", fwd),
+                   ("dgrad", lambda k: torch.autograd.grad(
+                       yd[k], x, gy, retain_graph=True)),
+                   ("wgrad", lambda k: torch.autograd.grad(
+                       yw[k], wt, gy, retain_graph=True)))
+            tot = {"1": [0.0] * passes, "0": [0.0] * passes}
+            for name, fn in ops:
+                rows = {"1": [], "0": []}
+                for i in range(passes):
+                    for knob in ("1", "0"):
+                        os.environ["DISTRIBUUUU_DW_TILE"] = knob
+                        rows[knob].append(timeit(lambda: fn(knob),
+                                                 iters=30, warmup=5))
+                        tot[knob][i] += rows[knob][-1]
+                fmt = lambda v: " ".join(  # noqa: E731
+                    f"{t*1e6:7.1f}" for t in v)
+                print(f"C={c:4d} {h:3d}x{h:<3d} {r}x{r} s{s} {name:5s} "
+                      f"tiled {fmt(rows['1'])} "
+                      f"({io/min(rows['1'])/1e9:5.0f} GB/s)"
+                      f" | packed {fmt(rows['0'])}")
+            os.environ.pop("DISTRIBUUUU_DW_TILE")
+            verdict = "keep" if max(tot["1"]) < min(tot["0"]) else "LOSES"
+            print(f"C={c:4d} {h:3d}x{h:<3d} {r}x{r} s{s} sum   "
+                  f"tiled {fmt(tot['1'])} | packed {fmt(tot['0'])} | "
+                  f"{verdict}")
+            del x, gy, yd, yw
+    finally:
+        os.environ.pop("DISTRIBUUUU_DW_TILE", None)
+        if saved is not None:
+            os.environ["DISTRIBUUUU_DW_TILE"] = saved
+
+
 # The in-range grouped 3x3 convs (C, w, H, stride), pad 1, of
 # resnext50_32x4d, then those only resnext101_32x8d has
 GCONV_SHAPES = [(128, 4, 56, 1), (256, 8, 56, 2), (256, 8, 28, 1),
@@ -803,6 +872,10 @@ if __name__ == "__main__":
     for a in args:
         if a.startswith("--slab-blocks="):
             slab_blocks = tuple(int(v) for v in a.split("=")[1].split(","))
+    dtype = "bf16"
+    for i, a in enumerate(args):
+        if a.startswith("--dtype"):  # --dtype fp32 or --dtype=fp32
+            dtype = a.split("=")[1] if "=" in a else args.pop(i + 1)
     groups = [a for a in args if not a.startswith("--")] or ["all"]
     if "bn" in groups or "all" in groups:
         bench_bn()
@@ -823,7 +896,7 @@ if __name__ == "__main__":
     if "se" in groups or "all" in groups:
         bench_se()
     if "dw" in groups or "all" in groups:
-        bench_dw()
+        bench_dw_f32() if dtype == "fp32" else bench_dw()
     if "gconv" in groups or "all" in groups:
         bench_gconv()
     if "dense" in groups or "all" in groups:
