@@ -162,6 +162,22 @@ std::tuple<std::string, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
 gconv_route_py(at::Tensor x, int64_t K, int64_t groups, int64_t R, int64_t S,
                int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh,
                int64_t dw, std::string pass);
+// gconv_tile_f32.hip
+at::Tensor gconv_f32_fwd(at::Tensor x, at::Tensor w, int64_t sh, int64_t sw,
+                         int64_t ph, int64_t pw, int64_t groups);
+std::tuple<at::Tensor, at::Tensor> gconv_f32_fwd_bn(at::Tensor x, at::Tensor w,
+                                                    int64_t sh, int64_t sw,
+                                                    int64_t ph, int64_t pw,
+                                                    int64_t groups);
+at::Tensor gconv_f32_dgrad(at::Tensor gy, at::Tensor w, int64_t H, int64_t W,
+                           int64_t sh, int64_t sw, int64_t ph, int64_t pw,
+                           int64_t groups);
+at::Tensor gconv_f32_wgrad(at::Tensor gy, at::Tensor x, int64_t sh, int64_t sw,
+                           int64_t ph, int64_t pw, int64_t groups);
+std::tuple<std::string, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
+gconv_f32_route_py(at::Tensor x, int64_t K, int64_t groups, int64_t R,
+                   int64_t S, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
+                   int64_t dh, int64_t dw, std::string pass);
 // se_gate.hip
 std::vector<at::Tensor> se_gate_fwd(at::Tensor p, at::Tensor w1, at::Tensor b1,
                                     at::Tensor w2, at::Tensor b2,
@@ -359,6 +375,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gconv_dgrad", &gconv_dgrad);
   m.def("gconv_wgrad", &gconv_wgrad);
   m.def("gconv_route", &gconv_route_py);
+  m.def("gconv_f32_fwd", &gconv_f32_fwd);
+  m.def("gconv_f32_fwd_bn", &gconv_f32_fwd_bn);
+  m.def("gconv_f32_dgrad", &gconv_f32_dgrad);
+  m.def("gconv_f32_wgrad", &gconv_f32_wgrad);
+  m.def("gconv_f32_route", &gconv_f32_route_py);
   m.def("mhsa_fwd", &mhsa_fwd);
   m.def("mhsa_bwd", &mhsa_bwd);
   m.def("mhsa_rel_tables", &mhsa_rel_tables);

@@ -113,3 +113,89 @@ inline GcRoute gconv_route(bool bf16_nhwc, int64_t N, int64_t C, int64_t K,
   r.tile = true;
   return r;
 }
+
+// ---------------------------------------------------------------------------
+// fp32 family (gconv_tile_f32.hip): the same range on fp32 NHWC tensors with
+// C % 4 == 0. An fp32 pixel is CW floats plus GCF_PAD: 36 or 68 dwords, so
+// sixteen lanes one pixel apart, 16 bytes each, start 4 * (9 i mod 16) or
+// 4 * (i mod 16) dwords apart and cover the 64 banks once.
+// ---------------------------------------------------------------------------
+constexpr int GCF_PAD = 4;  // floats of padding per LDS pixel (16 bytes)
+// the BN-partial epilogue meets in LDS: 256 threads x 8 floats
+constexpr int GCF_MIN_LDS = GC_THREADS * 8 * 4;
+// wgrad gates, in output pixels: stride 2 goes back from this size on at
+// w = 32 and w = 16, stride 1 at w = 32 below this size
+constexpr int GCF_W32_S2_WGRAD_OUT = 7 * 7;
+constexpr int GCF_W16_S2_WGRAD_OUT = 28 * 28;
+constexpr int GCF_W32_S1_WGRAD_OUT = 14 * 14;
+
+// log2 of the wave groups that split a wgrad block's tile rows; each writes
+// a workspace slot of its own, so the workspace has slots << this rows
+constexpr int gcf_wgrad_split(int CW) { return CW == 32 ? 1 : 0; }
+
+inline GcRoute gconv_f32_route(bool f32_nhwc, int64_t N, int64_t C, int64_t K,
+                               int64_t H, int64_t W, int64_t groups, int R,
+                               int S, int sh, int sw, int ph, int pw, int dh,
+                               int dw, GcPass pass,
+                               bool enabled = gconv_tile_enabled()) {
+  GcRoute r;
+  if (!enabled || !f32_nhwc || N < 1 || groups < 2 || R != 3 || S != 3 ||
+      dh != 1 || dw != 1 || sh != sw || (sh != 1 && sh != 2) || ph < 0 ||
+      pw < 0 || ph > 1 || pw > 1 || C < 8 || C % 4 != 0 || K != C ||
+      C % groups != 0 || H + 2 * ph < 3 || W + 2 * pw < 3 ||
+      H > (1 << 20) || W > (1 << 20) || N > (1 << 24) || C > (1 << 20))
+    return r;
+  const int64_t w = C / groups;
+  if (w != 4 && w != 8 && w != 16 && w != 32) return r;
+  const int st = sh;
+  const int Ho = (int)((H + 2 * ph - 3) / st + 1);
+  const int Wo = (int)((W + 2 * pw - 3) / st + 1);
+  // The measured losers (docs/ARCHITECTURE.md "Narrow-group conv, fp32"),
+  // all weight gradients, go back to conv2d_wgrad: a stride-2 patch leaves
+  // two output rows per tile, and at C = 1024 a 7x7 map has too few items
+  // per workspace slot.
+  if (pass == GcPass::Wgrad) {
+    const int64_t out = (int64_t)Ho * Wo;
+    if ((w == 32 && st == 2 && out >= GCF_W32_S2_WGRAD_OUT) ||
+        (w == 16 && st == 2 && out >= GCF_W16_S2_WGRAD_OUT) ||
+        (w == 32 && st == 1 && out < GCF_W32_S1_WGRAD_OUT))
+      return r;
+  }
+  // dgrad is the stride-1 machine over gy (stride 2: over its zero-inserted
+  // canvas) with gx as the output; fwd and wgrad tile the conv's output
+  const bool dg = pass == GcPass::Dgrad;
+  const int ms = dg ? 1 : st;
+  const int OH = dg ? (int)H : Ho, OW = dg ? (int)W : Wo;
+  // 64-channel chunks (256 B of a pixel) where the stride-1 patch leaves
+  // room for several tile rows; a stride-2 patch row is twice as long and
+  // the weight gradient holds the gy tile as well: 32
+  const int maxcw = (ms == 1 && pass != GcPass::Wgrad) ? 64 : 32;
+  r.nchunk = gc_ceil(C, maxcw);
+  r.CW = gc_ceil(gc_ceil(C, r.nchunk), 32) * 32;
+  const int pitch = (r.CW + GCF_PAD) * 4;
+  auto lds = [&](int th) {
+    int b = ((th - 1) * ms + 3) * gc_patch_cols(ms) * pitch;
+    if (pass == GcPass::Wgrad) b += th * GC_TW * pitch;
+    return std::max(b, GCF_MIN_LDS);
+  };
+  int th = gc_ceil(OH, gc_ceil(OH, GC_MAX_TH));
+  while (th > 1 && lds(th) > GC_LDS_BUDGET) --th;
+  r.TH = th;
+  r.lds_bytes = lds(th);
+  if (r.lds_bytes > GC_LDS_BUDGET) return r;
+  r.tilesH = gc_ceil(OH, th);
+  r.tilesW = gc_ceil(OW, GC_TW);
+  const int64_t items = N * r.tilesH * r.tilesW;
+  if (items >= ((int64_t)1 << 30)) return r;
+  const bool wg = pass == GcPass::Wgrad;
+  const int fill = wg ? GC_WGRAD_BLOCKS >> gcf_wgrad_split(r.CW)
+                      : GC_FILL_BLOCKS;
+  const int64_t cap = wg ? GC_MAX_SLOTS >> gcf_wgrad_split(r.CW)
+                         : GC_FILL_BLOCKS;
+  const int64_t want = std::clamp<int64_t>(gc_ceil(fill, r.nchunk), 1,
+                                           std::min<int64_t>(cap, items));
+  r.per = (int)((items + want - 1) / want);
+  r.slots = (int)((items + r.per - 1) / r.per);
+  r.tile = true;
+  return r;
+}

@@ -103,7 +103,9 @@ def set_fp32_precision(mode):
     with fp32 accumulation (the 3xBF16 scheme), about 2^-15 relative per
     product; shapes the split kernels do not cover keep the exact kernel.
     bf16 tensors are not affected, and neither are the fp32 attention kernels
-    (csrc/attention_fp32.hip): MHSA stays exact fp32 in both modes.
+    (csrc/attention_fp32.hip), the fp32 depthwise kernels
+    (csrc/depthwise_f32.hip) and the fp32 narrow-group conv kernels
+    (csrc/gconv_tile_f32.hip): they stay exact fp32 in both modes.
 
     The flag is sampled when a kernel is launched: a captured hipGraph keeps
     the mode it was captured in.

@@ -253,13 +253,13 @@ class _HIPDepthwiseConv2d(torch.autograd.Function):
         return gx, gw, gb, None, None, None
 
 
-def _gconv_wgrad(e, gy, x, geom):
-    """The weight gradient has a gate of its own (gconv_route sends the one
-    measured loser back to conv2d_wgrad)."""
+def _gconv_wgrad(e, gy, x, geom, pre="gconv"):
+    """The weight gradient has a gate of its own (the family's route sends
+    its measured losers back to conv2d_wgrad)."""
     sh, sw, ph, pw, groups = geom
-    if e.gconv_route(x, x.shape[1], groups, 3, 3, sh, sw, ph, pw, 1, 1,
-                     "wgrad")[0] == "tile":
-        return e.gconv_wgrad(gy, x, *geom)
+    if getattr(e, pre + "_route")(x, x.shape[1], groups, 3, 3, sh, sw, ph, pw,
+                                  1, 1, "wgrad")[0] == "tile":
+        return getattr(e, pre + "_wgrad")(gy, x, *geom)
     return e.conv2d_wgrad(gy, x, 3, 3, sh, sw, ph, pw, 1, 1, groups)
 
 
@@ -274,31 +274,34 @@ def _cl16(t):
 
 class _HIPGroupConv2d(torch.autograd.Function):
     """Narrow-group 3x3 convs (Cg == Kg in 4/8/16/32, ResNeXt's conv2) on the
-    LDS-tiled MFMA kernels of csrc/gconv_tile.hip. The raw weight is read as
-    it is: no packing, no prep kernel. ``emit_part`` as in _HIPConv2d."""
+    LDS-tiled MFMA kernels. ``pre`` names the kernel family: "gconv" (bf16,
+    csrc/gconv_tile.hip) or "gconv_f32" (exact fp32, csrc/gconv_tile_f32.hip).
+    The raw weight is read as it is: no packing, no prep kernel.
+    ``emit_part`` as in _HIPConv2d."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, stride, padding, groups, emit_part):
+    def forward(ctx, x, w, bias, stride, padding, groups, emit_part,
+                pre="gconv"):
         x = _cl16(x)
         w = _cl16(w)
         e = ext()
         geom = (stride[0], stride[1], padding[0], padding[1], groups)
         if emit_part and bias is None:
-            y, part = e.gconv_fwd_bn(x, w, *geom)
+            y, part = getattr(e, pre + "_fwd_bn")(x, w, *geom)
         else:
-            y = e.gconv_fwd(x, w, *geom)
+            y = getattr(e, pre + "_fwd")(x, w, *geom)
             part = y.new_empty(0)
         if bias is not None:
             y = y + bias.reshape(1, -1, 1, 1)
         ctx.save_for_backward(x, w)
-        ctx.conf = (geom, bias is not None)
+        ctx.conf = (geom, bias is not None, pre)
         ctx.mark_non_differentiable(part)
         return y, part
 
     @staticmethod
     def backward(ctx, gy, _gpart):
         x, w = ctx.saved_tensors
-        geom, has_bias = ctx.conf
+        geom, has_bias, pre = ctx.conf
         gy = _cl16(gy)
         e = ext()
         gx = gw = gb = None
@@ -308,9 +311,10 @@ class _HIPGroupConv2d(torch.autograd.Function):
             main = torch.cuda.current_stream()
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                gw = _gconv_wgrad(e, gy, x, geom)
+                gw = _gconv_wgrad(e, gy, x, geom, pre)
         if ctx.needs_input_grad[0]:
-            gx = e.gconv_dgrad(gy, w, x.shape[2], x.shape[3], *geom)
+            gx = getattr(e, pre + "_dgrad")(gy, w, x.shape[2], x.shape[3],
+                                            *geom)
         if side is not False:
             main.wait_stream(side)
             if not torch.cuda.is_current_stream_capturing():
@@ -318,29 +322,32 @@ class _HIPGroupConv2d(torch.autograd.Function):
                 gy.record_stream(side)
                 x.record_stream(side)
         elif ctx.needs_input_grad[1]:
-            gw = _gconv_wgrad(e, gy, x, geom)
+            gw = _gconv_wgrad(e, gy, x, geom, pre)
         if has_bias and ctx.needs_input_grad[2]:
             gb = gy.sum(dim=(0, 2, 3))
-        return gx, gw, gb, None, None, None, None
+        return gx, gw, gb, None, None, None, None, None
 
 
 def _gconv_tiled(x, weight, stride, padding, dilation, groups):
-    """The narrow-group route's answer for this conv (csrc/gconv_route.h).
-    Forward and data gradient share one range, so the forward's answer stands
-    for both; the weight gradient asks again (_gconv_wgrad)."""
-    if (groups < 2 or not x.is_cuda or x.dim() != 4 or weight.dim() != 4
-            or x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16
-            or weight.shape[2:] != (3, 3) or not use_hip(x, "gconv_fwd")):
-        return False
+    """The narrow-group route's answer for this conv (csrc/gconv_route.h):
+    the kernel family's prefix, "gconv" for bf16 and "gconv_f32" for fp32, or
+    None. Forward and data gradient share one range, so the forward's answer
+    stands for both; the weight gradient asks again (_gconv_wgrad)."""
+    pre = {torch.bfloat16: "gconv", torch.float32: "gconv_f32"}.get(x.dtype)
+    if (pre is None or groups < 2 or not x.is_cuda or x.dim() != 4
+            or weight.dim() != 4 or weight.dtype != x.dtype
+            or weight.shape[2:] != (3, 3) or not use_hip(x, pre + "_fwd")):
+        return None
     if not x.is_contiguous(memory_format=torch.channels_last):
         # the kernels get _cl(x): ask for that layout without making the
         # copy, which a "generic" answer would waste
         x = torch.empty(x.shape, dtype=x.dtype, device="meta",
                         memory_format=torch.channels_last)
-    return ext().gconv_route(
+    tiled = getattr(ext(), pre + "_route")(
         x, weight.shape[0], groups, weight.shape[2], weight.shape[3],
         stride[0], stride[1], padding[0], padding[1], dilation[0],
         dilation[1], "fwd")[0] == "tile"
+    return pre if tiled else None
 
 
 def _is_depthwise(x, weight, groups, dilation):
@@ -409,13 +416,14 @@ def conv2d(x, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
     if (x.dtype == torch.bfloat16 and _is_depthwise(x, weight, groups, dilation)
             and use_hip(x, "dwconv_fwd")):
         return _HIPDepthwiseConv2d.apply(x, weight, bias, stride, padding)
-    if _gconv_tiled(x, weight, stride, padding, dilation, groups):
+    gpre = _gconv_tiled(x, weight, stride, padding, dilation, groups)
+    if gpre:
         # the BN-partials protocol of the _HIPConv2d branch below; a
         # _fork_slot on x is ignored, so _Fork.backward does its plain add
         emit = (bias is None and torch.is_grad_enabled()
                 and getattr(weight, "_emit_bn_partials", False))
         y, part = _HIPGroupConv2d.apply(x, weight, bias, stride, padding,
-                                        groups, emit)
+                                        groups, emit, gpre)
         if part.numel():
             y._bn_partials = part
         elif bias is None:

@@ -560,27 +560,31 @@ GCONV_SHAPES = [(128, 4, 56, 1), (256, 8, 56, 2), (256, 8, 28, 1),
                 (1024, 32, 28, 2), (1024, 32, 14, 1)]
 
 
-def bench_gconv(n=128, passes=3):
+def bench_gconv(n=128, passes=3, dtype="bf16"):
     """Narrow-group 3x3 conv fwd / dgrad / wgrad through functional.conv2d:
     the LDS-tiled MFMA route next to the implicit-GEMM path
     (DISTRIBUUUU_GCONV_TILE=0; w = 4 packs 2:1 there), alternated over
     `passes` passes in one session. GB/s is against each pass's minimum
-    traffic: both activations once, the weight left out."""
+    traffic: both activations once, the weight left out. dtype "fp32" runs
+    the exact-fp32 family (gconv_f32_route) the same way."""
     import os
 
     from distribuuuu_amd.ops import functional as DF
 
-    print(f"== grouped 3x3 conv, tile vs igemm, ResNeXt at N={n} "
+    f32 = dtype == "fp32"
+    route_of = e.gconv_f32_route if f32 else e.gconv_route
+    print(f"== grouped 3x3 conv {dtype}, tile vs igemm, ResNeXt at N={n} "
           "(us per call; GB/s of minimum traffic) ==")
     saved = os.environ.pop("DISTRIBUUUU_GCONV_TILE", None)
     try:
         for c, w, h, s in GCONV_SHAPES:
             g, ho = c // w, (h - 1) // s + 1
-            bf = dict(device=DEV, dtype=torch.bfloat16)
+            bf = dict(device=DEV,
+                      dtype=torch.float32 if f32 else torch.bfloat16)
             x = _cl(torch.randn(n, c, h, h, **bf)).requires_grad_()
             wt = _cl(torch.randn(c, w, 3, 3, **bf) * 0.1).requires_grad_()
             gy = _cl(torch.randn(n, c, ho, ho, **bf))
-            io = (x.numel() + gy.numel()) * 2
+            io = (x.numel() + gy.numel()) * x.element_size()
             conv = lambda a, b: DF.conv2d(  # noqa: E731
                 a, b, None, (s, s), (1, 1), (1, 1), g)
             # one autograd graph per route and pass: a backward runs the
@@ -602,7 +606,7 @@ def bench_gconv(n=128, passes=3):
                    ("wgrad", lambda k: torch.autograd.grad(
                        yw[k], wt, gy, retain_graph=True)))
             for name, fn in ops:
-                route = e.gconv_route(x, c, g, 3, 3, s, s, 1, 1, 1, 1, name)
+                route = route_of(x, c, g, 3, 3, s, s, 1, 1, 1, 1, name)
                 rows = {"1": [], "0": []}
                 for _ in range(passes):
                     for knob in ("1", "0"):
@@ -898,7 +902,7 @@ if __name__ == "__main__":
     if "dw" in groups or "all" in groups:
         bench_dw_f32() if dtype == "fp32" else bench_dw()
     if "gconv" in groups or "all" in groups:
-        bench_gconv()
+        bench_gconv(dtype=dtype)
     if "dense" in groups or "all" in groups:
         bench_dense()
     if "fp32" in groups or "all" in groups:
